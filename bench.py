@@ -9,7 +9,17 @@ collective).  The other configs are reported as legs of the same line: chunk roo
 notary validation with the RCCL all-gather (configs[3]), BN254 pairing checks (configs[4]), and
 the §8f legs (Keccak-256 batch, tx roots, Proof of Custody, collation headers).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--legs a,b,..] [--dry-run]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py --full [--gpus N] [--steps K] [--warmup W] [--legs a,b,..] [--no-cpu-baseline]
+    python bench.py --dry-run [--gpus N] [--steps K]
+
+A plain run does what the headline figure needs and nothing else: it signs the batch, warms up, times
+exactly K steps of the default workload and prints the line (metric, value, unit, ms_per_step, ...).
+--full adds everything else to the same line as before: the other legs (--legs), the per-kernel
+instrumented passes and rooflines, and the CPU baselines with their parity checks.
+--dump-outputs DIR writes what the last timed step returned (public keys, addresses, statuses) of a
+fixed, seeded sample of OUTPUT_SAMPLE signatures as DIR/pubkey.npy, address.npy, status.npy (float32,
+one byte per element).  The inputs depend only on the arguments, so two builds compare file for file.
 
 --gpus N > 1 without torch.distributed's environment: bench.py starts N rank processes itself
 (python -m torch.distributed.run, one per GPU, 127.0.0.1) before anything touches a GPU, and exits
@@ -38,6 +48,8 @@ sys.path.insert(0, os.path.join(ROOT, "geth-sharding_amd"))
 sys.path.insert(0, ROOT)
 
 N_SIGS = 1 << 20          # configs[1]
+OUTPUT_SAMPLE = 1 << 16   # --dump-outputs: signatures sampled from the last timed step (86 bytes each)
+OUTPUT_SAMPLE_SEED = 20240
 N_SHARDS = 100            # configs[2]/[3]
 BODY = 1 << 20            # collation size limit (sharding/collation.go:45)
 NOTARY_TXS = 8192         # configs[3]: 8,192 x 128-byte blob-serialized txs = one 2^20-byte body
@@ -372,6 +384,17 @@ def cpu_sender(threads_all):
 
 
 # ----------------------------------------------------------------------------- GPU legs
+def output_sample():
+    """The rows of the 2^20-signature batch that --dump-outputs writes (fixed, sorted)."""
+    return np.sort(np.random.default_rng(OUTPUT_SAMPLE_SEED).choice(N_SIGS, OUTPUT_SAMPLE, replace=False))
+
+
+def dump_outputs(path, outputs):
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32))
+
+
 def leg_ecrecover(ctx, stream, dev, ws, rank, args):
     import torch
     from gsv import _lib
@@ -413,7 +436,7 @@ def leg_ecrecover(ctx, stream, dev, ws, rank, args):
     # one stream (the default): the kernel time comes from HIP events around every launch of the timed
     # region itself; batches in flight on several streams would overlap those event pairs, so there
     # it comes from a separate instrumented pass on one of the (warm) streams after the timed region
-    live = edepth == 1
+    live = edepth == 1 and args.full
     if live:
         ctx.reset_timing()
         ctx.set_timing(True)
@@ -425,8 +448,18 @@ def leg_ecrecover(ctx, stream, dev, ws, rank, args):
         s_.synchronize()
     barrier(ws)
     dt = max_over_ranks(time.perf_counter() - t0, ws)
+    state = {"msg": msg, "sig": sig, "epub": epub}
+    if args.dump_outputs and rank == 0:  # what the last timed step wrote, before anything else runs
+        p_, a_, s2_ = eouts[(args.steps - 1) % edepth]
+        rows = torch.from_numpy(output_sample()).to(dev)
+        state["outputs"] = {"pubkey": p_[rows].cpu().numpy(), "address": a_[rows].cpu().numpy(),
+                            "status": s2_[rows].cpu().numpy()}
     for p_, a_, s2_ in eouts:
         assert torch.equal(p_, epub) and torch.equal(a_, eaddr), "recovered keys differ from signers"
+    rate = ws * N_SIGS * args.steps / dt
+    if not args.full:  # the kernel time and the roofline take an instrumented pass of their own
+        ctx.destroy_streams(estreams)
+        return {"rate": rate, "dt": dt, "roofline": None}, state
     if not live:
         ctx.reset_timing()
         ctx.set_timing(True)
@@ -438,7 +471,6 @@ def leg_ecrecover(ctx, stream, dev, ws, rank, args):
     k_ms, k_n = ctx.kernel_time(_lib.K_ECRECOVER)
     k_avg_ms = max_over_ranks(k_ms / max(k_n, 1), ws)
     k_launches = int(k_n)
-    rate = ws * N_SIGS * args.steps / dt
     k = pmc("gsv::k_ecrecover", "pmc_ecrecover.json")
     ref_ach = MACS_PER_RECOVERY_REF * N_SIGS / (k_avg_ms * 1e-3)
     oc = opcount("recovery")
@@ -466,7 +498,6 @@ def leg_ecrecover(ctx, stream, dev, ws, rank, args):
                                     "(libsecp256k1 Strauss-wNAF), mac_equiv_per_recovery_actual = the "
                                     "v_mad_u64_u32 our kernel executes per recovery (9x29-bit fe9 products 108, "
                                     "squarings 72, dot products 189; GLV w=4 + comb; instrumented build, profiles/{ROUND}/opcount.json)".format(ROUND=ROUND)}
-    state = {"msg": msg, "sig": sig, "epub": epub}
     return {"rate": rate, "dt": dt, "roofline": roof}, state
 
 
@@ -1166,7 +1197,12 @@ def main():
     # run still finishes in about a minute)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=4)
-    ap.add_argument("--legs", default=",".join(LEGS), help="comma list of " + ",".join(LEGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also run the other legs, the per-kernel instrumented passes and rooflines, and the "
+                         "CPU baselines with their parity checks (a plain run times the headline leg only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs (a fixed sample of the batch) as DIR/<name>.npy")
+    ap.add_argument("--legs", help="with --full: comma list of " + ",".join(LEGS) + " (default: all)")
     ap.add_argument("--ecrecover-pipeline", type=int, default=2,
                     help="streams consecutive ecrecover (and collation-header) batches are spread over (2, the "
                          "default since r06: two batches in flight on dedicated-queue streams, as the other legs; "
@@ -1188,12 +1224,16 @@ def main():
                          "reads 1.125 ms per step four deep against 1.16-1.20 three deep, 100 shards equal at "
                          "2-4, profiles/r06/ab/notary_share_depths.txt)")
     ap.add_argument("--dry-run", action="store_true", help="CPU/gloo rank plumbing only (no GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     args = ap.parse_args()
-    legs = [x for x in args.legs.split(",") if x]
+    if not args.full and not args.dry_run and (args.legs is not None or args.no_cpu_baseline):
+        ap.error("--legs and --no-cpu-baseline belong to --full (a plain run times the ecrecover leg only)")
+    legs = [x for x in args.legs.split(",") if x] if args.legs is not None else (LEGS if args.full else ["ecrecover"])
     bad = [x for x in legs if x not in LEGS]
     if bad:
         ap.error(f"unknown legs {bad}")
+    if args.dump_outputs and "ecrecover" not in legs:
+        ap.error("--dump-outputs writes the ecrecover leg's outputs")
 
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
@@ -1233,8 +1273,11 @@ def main():
     if "pairing" in legs:
         res["pairing"], state["pairing"] = leg_pairing(ctx, stream, dev, ws, rank, args)
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, state["ecrecover"]["outputs"])
+
     cpu = None
-    if rank == 0 and ws == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and ws == 1 and not args.no_cpu_baseline:
         info = host_info()
         legs_cpu = cpu_baselines(ctx, legs, state, res, info)
         ec = legs_cpu.get("ecrecover")

@@ -54,6 +54,29 @@ def test_bench_eight_ranks_configs3_geometry():
     assert line["config"]["rank0_shards"] == [0, 12]
 
 
+def test_legs_belong_to_full():
+    """a plain run times the headline leg only: asking for other legs without --full is an error"""
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--legs", "chunk_root"], env=_env(),
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode == 2 and "--full" in p.stderr
+
+
+def test_dump_outputs_sample_and_files(tmp_path):
+    """--dump-outputs: the sampled rows are the same in every run, and the files are float32 .npy
+    holding the bytes exactly, within the 64 MB a dump may take"""
+    import numpy as np
+    import bench
+    rows = bench.output_sample()
+    assert rows.shape == (bench.OUTPUT_SAMPLE,) and (np.diff(rows) > 0).all()
+    assert rows[0] >= 0 and rows[-1] < bench.N_SIGS and (rows == bench.output_sample()).all()
+    assert bench.OUTPUT_SAMPLE * (65 + 20 + 1) * 4 <= 64e6
+    out = {"pubkey": np.arange(130, dtype=np.uint8).reshape(2, 65) + 126, "status": np.zeros(2, np.uint8)}
+    bench.dump_outputs(str(tmp_path / "d"), out)
+    for name, a in out.items():
+        b = np.load(tmp_path / "d" / (name + ".npy"))
+        assert b.dtype == np.float32 and b.shape == a.shape and (b == a).all()
+
+
 def test_world_size_must_match_gpus():
     e = _env()
     e.update(WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")

@@ -13,7 +13,7 @@ tail -1 $O/tests_bl.log
 for rep in 1 2 3; do
   for v in base bl; do
     if [ $v = base ]; then L=""; else L="variants/$v/libgsv.so"; fi
-    GSV_LIB_PATH=$L timeout -k 10 300 python3 bench.py --legs chunk_root --no-cpu-baseline > $O/bench_${v}_r$rep.log 2>&1 || { echo "$v bench failed"; tail -5 $O/bench_${v}_r$rep.log; exit 1; }
+    GSV_LIB_PATH=$L timeout -k 10 300 python3 bench.py --full --legs chunk_root --no-cpu-baseline > $O/bench_${v}_r$rep.log 2>&1 || { echo "$v bench failed"; tail -5 $O/bench_${v}_r$rep.log; exit 1; }
     tail -1 $O/bench_${v}_r$rep.log | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); c=d['chunk_root']
 print('$v r$rep chunk_root', c['ms_per_step'], 'ms/step', round(100*2**20/c['ms_per_step']/1e6,1), 'GB/s, bottom', c['roofline']['kernel_avg_ms'], 'ms')"
@@ -22,7 +22,7 @@ done
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for v in base bl; do
   if [ $v = base ]; then L=""; else L="variants/$v/libgsv.so"; fi
-  GSV_LIB_PATH=$L timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/tr_$v -o run -- python3 bench.py --legs chunk_root --no-cpu-baseline --steps 6 --warmup 2 --pipeline 1 > $O/tr_$v.log 2>&1 || { echo "$v trace failed"; tail -5 $O/tr_$v.log; exit 1; }
+  GSV_LIB_PATH=$L timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/tr_$v -o run -- python3 bench.py --full --legs chunk_root --no-cpu-baseline --steps 6 --warmup 2 --pipeline 1 > $O/tr_$v.log 2>&1 || { echo "$v trace failed"; tail -5 $O/tr_$v.log; exit 1; }
   python3 - $O/tr_$v $v <<'PY'
 import csv, glob, sys
 for f in glob.glob(sys.argv[1] + "/**/*kernel_stats.csv", recursive=True):

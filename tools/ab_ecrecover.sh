@@ -8,7 +8,7 @@ for v in base "$@"; do
   GSV_LIB_PATH=$L timeout -k 10 300 python -u -m pytest tests/test_gpu_secp256k1.py -x -q --timeout 120 \
       --timeout-method thread > gpurun_out/abe/test_$v.log 2>&1 || { echo "$v tests failed"; exit 1; }
   for i in 1 2 3; do
-    GSV_LIB_PATH=$L timeout -k 10 200 python bench.py --legs ecrecover --no-cpu-baseline --steps 20 \
+    GSV_LIB_PATH=$L timeout -k 10 200 python bench.py --full --legs ecrecover --no-cpu-baseline --steps 20 \
         > gpurun_out/abe/bench_$v.log 2>&1 || exit 1
     tail -1 gpurun_out/abe/bench_$v.log | python3 -c "
 import json, sys

@@ -10,7 +10,7 @@ export PYTHONUNBUFFERED=1
 for rep in 1 2; do
   for v in base glm65536 glm262144 glm1073741824; do
     if [ $v = base ]; then L=""; else L="variants/$v/libgsv.so"; fi
-    GSV_LIB_PATH=$L timeout -k 10 300 python3 bench.py --legs tx_root,chunk_root,poc --no-cpu-baseline > $O/bench_${v}_r$rep.log 2>&1 || { echo "$v bench failed"; tail -5 $O/bench_${v}_r$rep.log; exit 1; }
+    GSV_LIB_PATH=$L timeout -k 10 300 python3 bench.py --full --legs tx_root,chunk_root,poc --no-cpu-baseline > $O/bench_${v}_r$rep.log 2>&1 || { echo "$v bench failed"; tail -5 $O/bench_${v}_r$rep.log; exit 1; }
     tail -1 $O/bench_${v}_r$rep.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); e=d['collation_extras']; print('$v', 'tx_root', e['tx_root']['txs_per_s'], e['tx_root']['ms_per_step'], 'ms | chunk', d['chunk_root']['collation_GBps'], 'GB/s | poc', e['proof_of_custody']['bodies_per_s'])"
   done
 done

@@ -14,7 +14,7 @@ tail -1 $O/tests.log
 for rep in 1 2; do
   for v in base kold; do
     if [ $v = base ]; then L=""; else L="variants/$v/libgsv.so"; fi
-    GSV_LIB_PATH=$L timeout -k 10 300 python3 bench.py --legs chunk_root,keccak --no-cpu-baseline > $O/bench_${v}_r$rep.log 2>&1 || { echo "$v bench failed"; tail -5 $O/bench_${v}_r$rep.log; exit 1; }
+    GSV_LIB_PATH=$L timeout -k 10 300 python3 bench.py --full --legs chunk_root,keccak --no-cpu-baseline > $O/bench_${v}_r$rep.log 2>&1 || { echo "$v bench failed"; tail -5 $O/bench_${v}_r$rep.log; exit 1; }
     tail -1 $O/bench_${v}_r$rep.log | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); c=d['chunk_root']; k=d['collation_extras']['keccak256']
 print('$v chunk_root', c['ms_per_step'], 'ms/step', c['level_kernels_ms_per_step'], 'level ms', 'frac', c['roofline']['frac'],
@@ -24,7 +24,7 @@ done
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for v in base kold; do
   if [ $v = base ]; then L=""; else L="variants/$v/libgsv.so"; fi
-  GSV_LIB_PATH=$L timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/tr_$v -o run -- python3 bench.py --legs chunk_root,keccak --no-cpu-baseline --steps 6 --warmup 2 --pipeline 1 > $O/tr_$v.log 2>&1 || { echo "$v trace failed"; tail -5 $O/tr_$v.log; exit 1; }
+  GSV_LIB_PATH=$L timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/tr_$v -o run -- python3 bench.py --full --legs chunk_root,keccak --no-cpu-baseline --steps 6 --warmup 2 --pipeline 1 > $O/tr_$v.log 2>&1 || { echo "$v trace failed"; tail -5 $O/tr_$v.log; exit 1; }
   python3 - $O/tr_$v $v <<'PY'
 import csv, glob, sys
 for f in glob.glob(sys.argv[1] + "/**/*kernel_stats.csv", recursive=True):

@@ -15,7 +15,7 @@ for r in 1 2; do
     if [ $v = base ]; then L=""; else L="variants/$v/libgsv.so"; fi
     GSV_LIB_PATH=$L timeout -k 10 120 python tools/keccak_scale.py 400000 1600000 > $O/scale_${v}_$r.txt 2>&1 || { echo "$v scale failed"; tail -5 $O/scale_${v}_$r.txt; exit 1; }
     sed "s/^/$v /" $O/scale_${v}_$r.txt
-    GSV_LIB_PATH=$L timeout -k 10 200 python bench.py --legs keccak --no-cpu-baseline --steps 20 > $O/bench_${v}_$r.log 2>&1 || { echo "$v bench failed"; exit 1; }
+    GSV_LIB_PATH=$L timeout -k 10 200 python bench.py --full --legs keccak --no-cpu-baseline --steps 20 > $O/bench_${v}_$r.log 2>&1 || { echo "$v bench failed"; exit 1; }
     tail -1 $O/bench_${v}_$r.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read())['collation_extras']['keccak256']; print('$v leg', d['hashes_per_s'], d['ms_per_step'], d['roofline']['kernel_avg_ms'], d['roofline']['frac'])"
   done
 done

@@ -15,7 +15,7 @@ for rep in 1 2; do
     if [ $v = base ]; then L=""; else L="variants/$v/libgsv.so"; fi
     GSV_LIB_PATH=$L GSV_MAX_SIDE_STREAMS=0 NOTARY_DEPTHS=1 NOTARY_STEPS=12 timeout -k 10 300 python3 tools/notary_sweep.py 128 100 > $O/${v}_r$rep.txt 2>&1 || { echo "$v sweep failed"; tail $O/${v}_r$rep.txt; exit 1; }
     grep shards $O/${v}_r$rep.txt | sed "s/^/$v /"
-    GSV_LIB_PATH=$L timeout -k 10 300 python3 bench.py --legs notary --no-cpu-baseline > $O/bench_${v}_r$rep.log 2>&1 || { echo "$v bench failed"; tail -5 $O/bench_${v}_r$rep.log; exit 1; }
+    GSV_LIB_PATH=$L timeout -k 10 300 python3 bench.py --full --legs notary --no-cpu-baseline > $O/bench_${v}_r$rep.log 2>&1 || { echo "$v bench failed"; tail -5 $O/bench_${v}_r$rep.log; exit 1; }
     tail -1 $O/bench_${v}_r$rep.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read())['notary']; print('$v leg', d['shards_per_s'], 'shards/s', d.get('ms_per_step'), 'ms/step')"
   done
 done

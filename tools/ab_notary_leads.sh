@@ -18,7 +18,7 @@ for rep in 1 2; do
     grep shards $O/${v}_d1_r$rep.txt | sed "s/^/$v /"
     GSV_LIB_PATH=$L NOTARY_DEPTHS=4 timeout -k 10 300 python3 tools/notary_sweep.py 13 > $O/${v}_d4_r$rep.txt 2>&1 || { echo "$v sweep4 failed"; tail $O/${v}_d4_r$rep.txt; exit 1; }
     grep shards $O/${v}_d4_r$rep.txt | sed "s/^/$v /"
-    GSV_LIB_PATH=$L timeout -k 10 300 python3 bench.py --legs notary --no-cpu-baseline > $O/bench_${v}_r$rep.log 2>&1 || { echo "$v bench failed"; tail -5 $O/bench_${v}_r$rep.log; exit 1; }
+    GSV_LIB_PATH=$L timeout -k 10 300 python3 bench.py --full --legs notary --no-cpu-baseline > $O/bench_${v}_r$rep.log 2>&1 || { echo "$v bench failed"; tail -5 $O/bench_${v}_r$rep.log; exit 1; }
     tail -1 $O/bench_${v}_r$rep.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read())['notary']; print('$v leg', d['shards_per_s'], 'shards/s', d.get('ms_per_step'), 'ms/step')"
   done
 done

@@ -10,6 +10,6 @@ export PYTHONUNBUFFERED=1
 for rep in 1 2; do
   GSV_MAX_SIDE_STREAMS=0 NOTARY_DEPTHS=1 NOTARY_STEPS=12 timeout -k 10 300 python3 tools/notary_sweep.py 100 128 64 > $O/notary_r$rep.txt 2>&1 || { echo "sweep failed"; tail $O/notary_r$rep.txt; exit 1; }
   grep shards $O/notary_r$rep.txt
-  timeout -k 10 300 python3 bench.py --legs ecrecover --no-cpu-baseline --steps 20 > $O/ecr_r$rep.log 2>&1 || { echo "bench failed"; tail $O/ecr_r$rep.log; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --legs ecrecover --no-cpu-baseline --steps 20 > $O/ecr_r$rep.log 2>&1 || { echo "bench failed"; tail $O/ecr_r$rep.log; exit 1; }
   tail -1 $O/ecr_r$rep.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('ecrecover', d['value'], 'recoveries/s', d['ms_per_step'], 'ms per 2^20, kernel', d['roofline'].get('kernel_avg_ms'))"
 done

@@ -4,7 +4,7 @@
 set -o pipefail
 mkdir -p gpurun_out/p
 for d in "${@:-1 2 3}"; do
-  timeout -k 10 200 python bench.py --legs chunk_root,pairing --no-cpu-baseline --steps 40 --pipeline $d \
+  timeout -k 10 200 python bench.py --full --legs chunk_root,pairing --no-cpu-baseline --steps 40 --pipeline $d \
       --pairing-pipeline $d > gpurun_out/p/bench_d$d.log 2>&1 || exit 1
   tail -1 gpurun_out/p/bench_d$d.log | python3 -c "
 import json, sys

@@ -2,7 +2,7 @@
 
     python tools/ab_variants.py <leg> <variant|main> [...]
 
-Runs `bench.py --legs <leg> --no-cpu-baseline` once per variant in its own process
+Runs `bench.py --full --legs <leg> --no-cpu-baseline` once per variant in its own process
 (GSV_LIB_PATH=variants/<name>/libgsv.so; "main" = the in-tree library) and prints the leg's
 throughput and kernel time.  Every run keeps bench.py's full-size parity assertions.
 """
@@ -34,7 +34,7 @@ def main():
         env = dict(os.environ)
         if v != "main":
             env["GSV_LIB_PATH"] = os.path.join(ROOT, "variants", v, "libgsv.so")
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--legs", leg, "--no-cpu-baseline"] + extra,
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--legs", leg, "--no-cpu-baseline"] + extra,
                            env=env, capture_output=True, text=True, timeout=600)
         lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
         if p.returncode or not lines:

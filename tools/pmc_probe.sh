@@ -11,7 +11,7 @@ cd $GRAFT_REPO_ROOT
 i=0
 for C in "$@"; do
     i=$((i+1))
-    timeout -s KILL 200 rocprofv3 --pmc $C -f csv -d $OUT/p$i -o run -- python3 bench.py --legs $LEG --steps 1 --warmup 1 --no-cpu-baseline > $OUT/p$i.log 2>&1 || { echo "pass $i failed"; exit 1; }
+    timeout -s KILL 200 rocprofv3 --pmc $C -f csv -d $OUT/p$i -o run -- python3 bench.py --full --legs $LEG --steps 1 --warmup 1 --no-cpu-baseline > $OUT/p$i.log 2>&1 || { echo "pass $i failed"; exit 1; }
 done
 python3 - $OUT > $OUT/summary.txt <<'PY'
 import csv, glob, sys, collections

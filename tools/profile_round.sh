@@ -20,7 +20,7 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 for G in $GROUPS_; do
     if [ $G = all ]; then
-        timeout -k 10 300 rocprofv3 --kernel-trace --stats -f rocpd csv -d $OUT/all/trace -o run -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/trace.log 2>&1 || { echo "trace pass failed"; exit 1; }
+        timeout -k 10 300 rocprofv3 --kernel-trace --stats -f rocpd csv -d $OUT/all/trace -o run -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/trace.log 2>&1 || { echo "trace pass failed"; exit 1; }
         find $OUT/all/trace -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;
         continue
     fi
@@ -28,7 +28,7 @@ for G in $GROUPS_; do
     # the notary step forks its chunk roots beside its transactions: no side streams in the leg-only
     # passes, so every traced dispatch runs alone (tools/pmc_summary.py drops any that still overlap)
     if [ $G = notary ]; then export GSV_MAX_SIDE_STREAMS=0; else unset GSV_MAX_SIDE_STREAMS; fi
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats -f rocpd csv -d $OUT/$G/trace -o run -- python3 bench.py $B > $OUT/$G.trace.log 2>&1 || { echo "trace pass $G failed"; exit 1; }
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats -f rocpd csv -d $OUT/$G/trace -o run -- python3 bench.py --full $B > $OUT/$G.trace.log 2>&1 || { echo "trace pass $G failed"; exit 1; }
     find $OUT/$G/trace -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats_$G.csv \;
     # per-dispatch start / end of the library's kernels (small): tools/trace_agreement.py compares the
     # bench's instrumented launches with the same launches here (the first launches of a process read slow)
@@ -43,10 +43,10 @@ with open(sys.argv[2], "w") as o:
         if "gsv::" in n:
             o.write(f"{n.replace(',', ';')},{r['Start_Timestamp']},{r['End_Timestamp']}\n")
 PY
-    timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE -d $OUT/$G/fetch -o run -- python3 bench.py $B > $OUT/$G.fetch.log 2>&1 || { echo "fetch pass $G failed"; exit 1; }
-    timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE -d $OUT/$G/write -o run -- python3 bench.py $B > $OUT/$G.write.log 2>&1 || { echo "write pass $G failed"; exit 1; }
-    timeout -s KILL 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE -d $OUT/$G/sq -o run -- python3 bench.py $B > $OUT/$G.sq.log 2>&1 || { echo "sq pass $G failed"; exit 1; }
-    timeout -s KILL 300 rocprofv3 --pmc SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 GRBM_GUI_ACTIVE -d $OUT/$G/int -o run -- python3 bench.py $B > $OUT/$G.int.log 2>&1 || { echo "int pass $G failed"; exit 1; }
+    timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE -d $OUT/$G/fetch -o run -- python3 bench.py --full $B > $OUT/$G.fetch.log 2>&1 || { echo "fetch pass $G failed"; exit 1; }
+    timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE -d $OUT/$G/write -o run -- python3 bench.py --full $B > $OUT/$G.write.log 2>&1 || { echo "write pass $G failed"; exit 1; }
+    timeout -s KILL 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE -d $OUT/$G/sq -o run -- python3 bench.py --full $B > $OUT/$G.sq.log 2>&1 || { echo "sq pass $G failed"; exit 1; }
+    timeout -s KILL 300 rocprofv3 --pmc SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 GRBM_GUI_ACTIVE -d $OUT/$G/int -o run -- python3 bench.py --full $B > $OUT/$G.int.log 2>&1 || { echo "int pass $G failed"; exit 1; }
     python3 tools/pmc_summary.py $OUT/$G > $OUT/pmc_$G.json || { echo "summary $G failed"; exit 1; }
     echo "pass group $G done"
 done

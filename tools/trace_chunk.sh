@@ -5,7 +5,7 @@ OUT=gpurun_out/trace_chunk
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $OUT -o run -- python3 bench.py --workload chunk_root --steps 3 --warmup 1 --no-cpu-baseline > $OUT/log.txt 2>&1 || { echo "trace failed"; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $OUT -o run -- python3 bench.py --full --workload chunk_root --steps 3 --warmup 1 --no-cpu-baseline > $OUT/log.txt 2>&1 || { echo "trace failed"; exit 1; }
 python3 - <<'PY'
 import csv, glob
 f = glob.glob("gpurun_out/trace_chunk/**/run_kernel_trace.csv", recursive=True)[0]

@@ -8,7 +8,7 @@ rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 for d in 1 2; do
-  timeout -k 10 300 rocprofv3 --kernel-trace -f csv -d $OUT/d$d -o run -- python3 bench.py --legs chunk_root \
+  timeout -k 10 300 rocprofv3 --kernel-trace -f csv -d $OUT/d$d -o run -- python3 bench.py --full --legs chunk_root \
       --no-cpu-baseline --steps 20 --pipeline $d > $OUT/log_d$d.txt 2>&1 || { echo "trace failed"; exit 1; }
 done
 python3 - <<'PY'

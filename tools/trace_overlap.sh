@@ -8,7 +8,7 @@ OUT=gpurun_out/trace_ov
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-timeout -k 10 300 rocprofv3 --kernel-trace -f csv -d $OUT -o run -- python3 bench.py --legs chunk_root,pairing \
+timeout -k 10 300 rocprofv3 --kernel-trace -f csv -d $OUT -o run -- python3 bench.py --full --legs chunk_root,pairing \
     --no-cpu-baseline --steps 12 --pipeline 2 --pairing-pipeline 2 > $OUT/log.txt 2>&1 || { echo "trace failed"; exit 1; }
 python3 - <<'PY'
 import csv, glob
