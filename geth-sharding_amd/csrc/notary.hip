@@ -13,8 +13,12 @@
 // Outputs per shard: chunk root, tx count, validity bitmap (bit t = tx t's sender recovered), and
 // optionally per-tx sender addresses and status codes.
 //
-// The decode rules are the ones the host path uses (csrc/tx_host.hip tx_prepare), restated for one
-// lane: the blob's bytes are read through the chunk map (byte k at chunk k/31, offset 1 + k%31).
+// The decode rules are rlp/decode.go's for txdata, as the host path states them (csrc/tx_host.hip
+// tx_prepare; tests/tx_rules_model.py is the independent model all copies are tested against): uint64
+// fields of at most 8 bytes, *big.Int fields of any length, no leading zero in either, and the rlp:"nil"
+// recipient, which is nil for size 0 of string or list kind (0x80 or 0xc0, decode.go:486-496).  They are
+// restated for one lane: the blob's bytes are read through the chunk map (byte k at chunk k/31, offset
+// 1 + k%31).
 #include "opcount.cuh"
 #include "recover_dev.cuh"
 
@@ -184,12 +188,16 @@ GSV_DI uint32_t rlp_item(const BlobView& b, uint32_t p, uint32_t len, RItem& it)
     it.list = true;
     return 1 + n;
 }
+// uint64 (Stream.uint, decode.go:703-734): maxlen 8.  *big.Int (decodeBigInt, :271-287): any length
 GSV_DI bool uint_ok(const BlobView& b, const RItem& it, uint32_t maxlen) {
     return !it.list && it.n <= maxlen && !(it.n > 0 && b.at(it.off) == 0);
 }
-GSV_DI uint64_t item_u64(const BlobView& b, const RItem& it) {  // it.n <= 8
+// the item's low 64 bits: its last min(n, 8) bytes (V may be any length; callers use the whole value only
+// where bitlen_item says it fits)
+GSV_DI uint64_t item_u64(const BlobView& b, const RItem& it) {
     uint64_t v = 0;
-    for (uint32_t i = 0; i < it.n; i++) v = (v << 8) | b.at(it.off + i);
+    uint32_t k = it.n < 8u ? it.n : 8u;
+    for (uint32_t i = it.n - k; i < it.n; i++) v = (v << 8) | b.at(it.off + i);
     return v;
 }
 GSV_DI uint32_t bitlen_item(const BlobView& b, const RItem& it) {  // canonical: no leading zero
@@ -210,7 +218,8 @@ __device__ __noinline__ uint32_t v_big_path(const uint8_t* blob_base, uint32_t v
                                             const uint8_t* __restrict__ cid64, uint8_t* vv_low,
                                             uint32_t* vv_big) {
     BlobView b{blob_base, 0};  // at() only
-    if (vn > 64) return GSV_ST_INVALID_CHAIN_ID;  // be_sub rejects an > 64
+    // V >= 2^512: (V - 35) / 2 >= 2^511 - 18 differs from every chain id below 2^511
+    if (vn > 64) return GSV_ST_INVALID_CHAIN_ID;
     uint8_t V[64], t[64], chain[64];
     for (int i = 0; i < 64; i++) V[i] = 0;
     for (uint32_t i = 0; i < vn; i++) V[64 - vn + i] = b.at(voff + i);
@@ -259,6 +268,7 @@ struct PreStream {
     uint32_t seg_lo, seg_len;
     const uint8_t* suffix;  // uniform; zero bytes at [-8, 0) and [slen, slen + 8) (notary_shape layout)
     uint32_t slen;
+    uint32_t patch;  // stream position of a recipient sent as 0xc0, hashed as 0x80; PATCH_NONE otherwise
     GSV_DI uint32_t total() const { return hlen + seg_len + slen; }
     // stream bytes sp .. sp+3 (sp a multiple of 4) as one little-endian word, zero past the stream
     GSV_DI uint32_t dword(uint32_t sp, uint64_t hle) const {
@@ -283,6 +293,8 @@ struct PreStream {
     }
 };
 
+constexpr uint32_t PATCH_NONE = 0x80000000u;  // no stream is this long (bodies are <= 2^20 bytes)
+
 // Keccak-256 over the stream (crypto/sha3/sha3.go:98-157: rate 136, dsbyte 0x01), each rate block
 // gathered as 34 little-endian dwords: the blob bytes through BlobView::dword (two aligned loads per four
 // bytes, all of a block's loads independent), the header from a register, the suffix from its
@@ -298,9 +310,14 @@ GSV_DI void keccak_stream(uint64_t a[25], const PreStream& s) {
     while (true) {
         uint32_t rem = len - pos;  // bytes left; the final block when rem < 136
         bool final = rem < 136;
+        // a nil recipient sent as the empty list (0xc0) is re-encoded as 0x80: flip that one stream byte.
+        // pd wraps to >= 2^31 - 2^21 for blocks past the byte and for PATCH_NONE, so no word matches.
+        const uint32_t pd = s.patch - pos;
+        const uint64_t pm = 0x40ull << (8u * (pd & 7u));
 #pragma unroll
         for (int w = 0; w < 17; w++) {
             uint64_t v = (uint64_t)s.dword(pos + 8u * w, hle) | ((uint64_t)s.dword(pos + 8u * w + 4u, hle) << 32);
+            if ((pd >> 3) == (uint32_t)w) v ^= pm;
             if (final && (rem >> 3) == (uint32_t)w) v ^= 0x01ull << (8u * (rem & 7u));
             if (final && w == 16) v ^= 0x8000000000000000ULL;
             a[w] ^= v;
@@ -345,9 +362,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GSV_ECR_WAV
             rem -= u;
         }
         ok = ok && rem == 0;
-        ok = ok && uint_ok(b, f[0], 8) && uint_ok(b, f[2], 8) && uint_ok(b, f[1], 256) && uint_ok(b, f[4], 256) &&
-             uint_ok(b, f[6], 256) && uint_ok(b, f[7], 256) && uint_ok(b, f[8], 256);
-        ok = ok && !f[3].list && (f[3].n == 0 || f[3].n == 20) && !f[5].list;
+        ok = ok && uint_ok(b, f[0], 8) && uint_ok(b, f[2], 8) && uint_ok(b, f[1], ~0u) && uint_ok(b, f[4], ~0u) &&
+             uint_ok(b, f[6], ~0u) && uint_ok(b, f[7], ~0u) && uint_ok(b, f[8], ~0u);
+        // Recipient is rlp:"nil": size 0 of either kind is nil, else a 20-byte string
+        ok = ok && (f[3].n == 0 || (!f[3].list && f[3].n == 20)) && !f[5].list;
         if (ok) {
             st = GSV_ST_OK;
             // signer (transaction_signing.go:127-137 EIP155, :182-184 Homestead, :218-220 Frontier)
@@ -394,8 +412,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GSV_ECR_WAV
                 vbig = vb > 8;
                 vbyte = (uint32_t)(item_u64(b, f[6]) & 0xFF);
             }
-            // sighash = Keccak(rlp([nonce, gasPrice, gas, to, value, data (, chainId, 0, 0)])):
-            // the six canonical items are re-encoded byte for byte, so they are one slice of the tx
+            // sighash = Keccak(rlp([nonce, gasPrice, gas, to, value, data (, chainId, 0, 0)])): the six
+            // items are canonical, so their re-encoding is one slice of the tx, except a nil recipient
+            // sent as 0xc0, which the signer re-encodes as 0x80 (PreStream::patch)
             PreStream ps;
             ps.b = b;
             ps.seg_lo = f[0].start;
@@ -411,6 +430,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GSV_ECR_WAV
                 ps.hdr = ((uint64_t)(0xf7 + nb) << (8 * nb)) | body_len;
                 ps.hlen = 1 + nb;
             }
+            ps.patch = f[3].list ? ps.hlen + (f[3].start - f[0].start) : PATCH_NONE;
             uint64_t a[25];
             keccak_stream(a, ps);
 #pragma unroll

@@ -146,10 +146,15 @@ int tx_prepare(const uint8_t* rlp, size_t len, const uint8_t* cid, size_t cidlen
         rem -= u;
     }
     if (rem) return GSV_ST_BAD_RLP;
-    if (!uint_ok(f[0], 8) || !uint_ok(f[2], 8) || !uint_ok(f[1], 256) || !uint_ok(f[4], 256) ||
-        !uint_ok(f[6], 256) || !uint_ok(f[7], 256) || !uint_ok(f[8], 256))
+    // uint64 fields: at most 8 bytes (Stream.uint, rlp/decode.go:703-734); *big.Int fields: any length
+    // (decodeBigInt, :271-287)
+    const size_t any = (size_t)-1;
+    if (!uint_ok(f[0], 8) || !uint_ok(f[2], 8) || !uint_ok(f[1], any) || !uint_ok(f[4], any) ||
+        !uint_ok(f[6], any) || !uint_ok(f[7], any) || !uint_ok(f[8], any))
         return GSV_ST_BAD_RLP;
-    if (f[3].list || (f[3].n != 0 && f[3].n != 20) || f[5].list) return GSV_ST_BAD_RLP;
+    // Recipient is rlp:"nil" (makeOptionalPtrDecoder, rlp/decode.go:486-496): size 0 of string or list
+    // kind (0x80, 0xc0) is nil; anything else must be a 20-byte string (decodeByteArray, :395-430)
+    if ((f[3].n != 0 && (f[3].list || f[3].n != 20)) || f[5].list) return GSV_ST_BAD_RLP;
 
     auto sighash_pre = [&](bool eip155) {
         std::vector<uint8_t> body;
@@ -194,7 +199,7 @@ int tx_prepare(const uint8_t* rlp, size_t len, const uint8_t* cid, size_t cidlen
                 }
             }
             if (cidlen > 64) return GSV_ST_INVALID_CHAIN_ID;
-            memcpy(want + 64 - cidlen, cid, cidlen);
+            if (cidlen) memcpy(want + 64 - cidlen, cid, cidlen);  // chain id 0 may come as (NULL, 0)
             if (memcmp(chain, want, 64) != 0) return GSV_ST_INVALID_CHAIN_ID;
             uint8_t two_c[64], t[64], vv[64];
             int carry = 0;

@@ -507,7 +507,7 @@ static void buf_put(buf_t *b, const uint8_t *d, size_t n) {
         b->p = (uint8_t *)realloc(b->p, nc);
         b->cap = nc;
     }
-    memcpy(b->p + b->n, d, n);
+    if (n) memcpy(b->p + b->n, d, n); /* d may be NULL for an empty string */
     b->n += n;
 }
 static void rlp_header(buf_t *b, size_t len, uint8_t base) {
@@ -552,7 +552,7 @@ static size_t rlp_next(const uint8_t *p, size_t len, rlp_item *it) {
         size_t nb = b0 - 0xb7, n = 0;
         if (1 + nb > len || p[1] == 0) return 0;
         for (size_t i = 0; i < nb; i++) n = (n << 8) | p[1 + i];
-        if (n < 56 || 1 + nb + n > len) return 0;
+        if (n < 56 || n > len - 1 - nb) return 0; /* no sum: n may be near 2^64 */
         it->p = p + 1 + nb; it->n = n; it->is_list = 0; return 1 + nb + n;
     }
     if (b0 < 0xf8) {
@@ -563,7 +563,7 @@ static size_t rlp_next(const uint8_t *p, size_t len, rlp_item *it) {
     size_t nb = b0 - 0xf7, n = 0;
     if (1 + nb > len || p[1] == 0) return 0;
     for (size_t i = 0; i < nb; i++) n = (n << 8) | p[1 + i];
-    if (n < 56 || 1 + nb + n > len) return 0;
+    if (n < 56 || n > len - 1 - nb) return 0;
     it->p = p + 1 + nb; it->n = n; it->is_list = 1; return 1 + nb + n;
 }
 
@@ -573,6 +573,8 @@ typedef struct {
     int has_to;
 } txdata_t;
 
+/* uint64: Stream.uint (rlp/decode.go:703-734), at most 8 bytes.  *big.Int: decodeBigInt (:271-287),
+ * any length (maxlen = SIZE_MAX).  Both refuse a leading zero byte, a lone 0x00 included. */
 static int rlp_uint_ok(const rlp_item *it, size_t maxlen) {
     if (it->is_list || it->n > maxlen) return 0;
     if (it->n > 0 && it->p[0] == 0) return 0; /* leading zero */
@@ -598,10 +600,12 @@ static int tx_decode(txdata_t *tx, const uint8_t *rlp, size_t len) {
     }
     if (rem) return 0;
     if (!rlp_uint_ok(&f[0], 8) || !rlp_uint_ok(&f[2], 8)) return 0;
-    if (!rlp_uint_ok(&f[1], 32 * 8) || !rlp_uint_ok(&f[4], 32 * 8)) return 0;
-    if (!rlp_uint_ok(&f[6], 32 * 8) || !rlp_uint_ok(&f[7], 32 * 8) || !rlp_uint_ok(&f[8], 32 * 8))
+    if (!rlp_uint_ok(&f[1], SIZE_MAX) || !rlp_uint_ok(&f[4], SIZE_MAX)) return 0;
+    if (!rlp_uint_ok(&f[6], SIZE_MAX) || !rlp_uint_ok(&f[7], SIZE_MAX) || !rlp_uint_ok(&f[8], SIZE_MAX))
         return 0;
-    if (f[3].is_list || (f[3].n != 0 && f[3].n != 20)) return 0;
+    /* Recipient *common.Address `rlp:"nil"` (makeOptionalPtrDecoder, rlp/decode.go:486-496): size 0 of
+     * string OR list kind (0x80, 0xc0) is nil; else decodeByteArray (:395-430): a 20-byte string */
+    if (f[3].n != 0 && (f[3].is_list || f[3].n != 20)) return 0;
     if (f[5].is_list) return 0;
     tx->nonce = rlp_to_u64(&f[0]);
     tx->price = f[1];
@@ -744,7 +748,7 @@ static int tx_sender_decoded(uint8_t addr20[20], uint8_t sighash_out[32], const 
                 }
             }
             if (cidlen > 64) return OR_INVALID_CHAIN_ID;
-            memcpy(want + 64 - cidlen, cid, cidlen);
+            if (cidlen) memcpy(want + 64 - cidlen, cid, cidlen); /* chain id 0 may come as (NULL, 0) */
             if (memcmp(chain, want, 64) != 0) return OR_INVALID_CHAIN_ID;
             /* V = tx.V - 2*chainId - 8 */
             uint8_t two_c[64], vv[64];
