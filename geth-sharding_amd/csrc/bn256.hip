@@ -22,6 +22,7 @@
 // stores coalesce across the wave.
 #include "opcount.cuh"
 #include "bn254_fe9.cuh"
+#include "bn_g1.cuh"  // BN_P_W, fp_unmarshal, fp_marshal (shared with the G1 precompile kernels)
 #include "gsv_internal.h"
 #include "keccak_dev.cuh"
 
@@ -32,9 +33,6 @@ namespace bn {
 #define GSV_DI __device__ __forceinline__
 #endif
 
-// p as eight little-endian 32-bit words (constants.go:31 P)
-__device__ constexpr uint32_t BN_P_W[8] = {0xd87cfd47u, 0x3c208c16u, 0x6871ca8du, 0x97816a91u,
-                                           0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
 // sixuPlus2NAF (optate.go:114-118) digits 0..63 as two bit masks (digit 64 is the leading 1)
 constexpr uint64_t NAF_POS = 0xa1818041c0864428ULL;  // bit i set where digit i == +1
 constexpr uint64_t NAF_NEG = 0x0408100802100880ULL;  // bit i set where digit i == -1
@@ -385,38 +383,7 @@ GSV_DI line line_load(const uint32_t* __restrict__ lines, uint32_t n, uint32_t j
     return line{soa_load2(lines, n, j, li * 6 + 0), soa_load2(lines, n, j, li * 6 + 2), soa_load2(lines, n, j, li * 6 + 4)};
 }
 
-// gfP.Unmarshal (gfp.go:61-78) + montEncode: big-endian bytes -> Montgomery form (R = 2^261);
-// false if the coordinate is >= p
-GSV_DI bool fp_unmarshal(fq& r, const uint8_t* p) {
-    uint32_t x[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const uint8_t* q = p + 28 - 4 * i;
-        x[i] = ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | q[3];
-    }
-    int64_t br = 0;  // x - p: the final borrow says x < p
-#pragma unroll
-    for (int i = 0; i < 8; i++) br = ((int64_t)x[i] - (int64_t)BN_P_W[i] + br) >> 32;
-    bool ok = br != 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) x[i] = ok ? x[i] : 0u;
-    r = fq_store(fq_mul(fq_from_words(x), fq_const(FQ_R2)));
-    return ok;
-}
-// montDecode + big-endian marshal (gfp.go:51-59): the canonical residue of a R^-1
-GSV_DI void fp_marshal(uint8_t* out, const fq& a) {
-    fqm<1, 1> one{{1, 0, 0, 0, 0, 0, 0, 0, 0}};
-    uint32_t w[8];
-    fq_to_words(w, fq_canon(fq_mul(a, one)));
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        uint32_t x = w[7 - i];
-        out[4 * i] = (uint8_t)(x >> 24);
-        out[4 * i + 1] = (uint8_t)(x >> 16);
-        out[4 * i + 2] = (uint8_t)(x >> 8);
-        out[4 * i + 3] = (uint8_t)x;
-    }
-}
+// fp_unmarshal / fp_marshal (gfp.go:51-78): bn_g1.cuh
 
 // ---------------------------------------------------------------- kernels
 enum : uint8_t { PS_OK = 0, PS_SKIP = 1, PS_BAD = 2 };

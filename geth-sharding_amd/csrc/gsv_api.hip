@@ -818,6 +818,73 @@ int gsv_ecrecover_precompile_batch(gsv_ctx* c, const uint8_t* in, const uint64_t
     return GSV_SUCCESS;
 }
 
+// ------------------------------------------------------------------ bn256Add / bn256ScalarMul (contracts.go:274-312)
+// GSV_BN_G1_BITSERIAL=1 selects the bit-serial multiplication kernel (A/B timing and the tests only)
+static int bn_g1_bitserial() {
+    const char* e = getenv("GSV_BN_G1_BITSERIAL");
+    return e && atoi(e) != 0;
+}
+
+int gsv_bn256_add_batch_dev(gsv_ctx* c, const uint8_t* d_in128, size_t n, uint8_t* d_out64, uint8_t* d_status,
+                            void* stream) {
+    if (!c || (n && (!d_in128 || !d_out64 || !d_status)) || n > 0xFFFFFFFFull) return GSV_E_INVALID_ARG;
+    if (n == 0) return GSV_SUCCESS;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    KTimer t(c, GSV_K_BN_G1, st);
+    return hip_err(gsv::launch_bn256_g1_add(d_in128, (uint32_t)n, d_out64, d_status, st));
+}
+
+int gsv_bn256_scalar_mul_batch_dev(gsv_ctx* c, const uint8_t* d_in96, size_t n, uint8_t* d_out64, uint8_t* d_status,
+                                   void* stream) {
+    if (!c || (n && (!d_in96 || !d_out64 || !d_status)) || n > 0xFFFFFFFFull) return GSV_E_INVALID_ARG;
+    if (n == 0) return GSV_SUCCESS;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    KTimer t(c, GSV_K_BN_G1, st);
+    return hip_err(gsv::launch_bn256_g1_mul(d_in96, (uint32_t)n, d_out64, d_status, bn_g1_bitserial(), st));
+}
+
+// getData(input, 0, rec) (core/vm/common.go:37-47): right-pad with zeros, ignore what follows; stage,
+// launch, copy back
+static int bn_g1_host(gsv_ctx* c, const uint8_t* in, const uint64_t* off, size_t n, size_t rec, uint8_t* out64,
+                      uint8_t* status) {
+    if (!c || (n && (!off || !out64 || !status)) || n > 0xFFFFFFFFull) return GSV_E_INVALID_ARG;
+    if (n == 0) return GSV_SUCCESS;
+    for (size_t i = 0; i < n; i++)
+        if (off[i + 1] < off[i]) return GSV_E_INVALID_ARG;
+    if (off[n] > off[0] && !in) return GSV_E_INVALID_ARG;
+    std::vector<uint8_t> pad(n * rec, 0);
+    for (size_t i = 0; i < n; i++) {
+        size_t len = std::min<uint64_t>(off[i + 1] - off[i], rec);
+        if (len) memcpy(&pad[i * rec], in + off[i], len);
+    }
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    int rc = arena_reserve(c, al(n * rec) + al(n * 64) + al(n));
+    if (rc) return rc;
+    Carve cv(c->arena);
+    uint8_t* d_in = cv.take<uint8_t>(n * rec);
+    uint8_t* d_out = cv.take<uint8_t>(n * 64);
+    uint8_t* d_st = cv.take<uint8_t>(n);
+    HIPCHK(hipMemcpyAsync(d_in, pad.data(), n * rec, hipMemcpyHostToDevice, c->stream));
+    rc = rec == 128 ? gsv_bn256_add_batch_dev(c, d_in, n, d_out, d_st, c->stream)
+                    : gsv_bn256_scalar_mul_batch_dev(c, d_in, n, d_out, d_st, c->stream);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(out64, d_out, n * 64, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return GSV_SUCCESS;
+}
+
+int gsv_bn256_add_batch(gsv_ctx* c, const uint8_t* in, const uint64_t* off, size_t n, uint8_t* out64,
+                        uint8_t* status) {
+    return bn_g1_host(c, in, off, n, 128, out64, status);
+}
+
+int gsv_bn256_scalar_mul_batch(gsv_ctx* c, const uint8_t* in, const uint64_t* off, size_t n, uint8_t* out64,
+                               uint8_t* status) {
+    return bn_g1_host(c, in, off, n, 96, out64, status);
+}
+
 // ------------------------------------------------------------------ recoverPlain
 int gsv_sender_batch(gsv_ctx* c, const uint8_t* sighash32, const uint8_t* r32, const uint8_t* s32,
                      const uint64_t* v, const uint8_t* v_big, size_t n, int homestead,

@@ -76,6 +76,14 @@ hipError_t launch_bn256_pairing(const uint8_t* d_in, const uint64_t* d_pair_src,
                                 void (*timer_end)(void*, int), void* tctx);
 hipError_t launch_bn256_synth(uint64_t seed, uint32_t nchecks, uint8_t* d_out, uint8_t* d_expect, hipStream_t st);
 
+// bn_g1.hip: the bn256Add / bn256ScalarMul precompiles over fixed-size records (128 B / 96 B -> 64 B +
+// status).  bitserial != 0 selects the 256-step double-and-add form of the multiplication (the A/B
+// partner of the GLV path: tools/bn_g1_sweep.py and the tests only)
+hipError_t launch_bn256_g1_add(const uint8_t* d_in128, uint32_t n, uint8_t* d_out64, uint8_t* d_status,
+                               hipStream_t st);
+hipError_t launch_bn256_g1_mul(const uint8_t* d_in96, uint32_t n, uint8_t* d_out64, uint8_t* d_status,
+                               int bitserial, hipStream_t st);
+
 // notary.hip
 size_t blob_rec_bytes();
 hipError_t launch_partition_pack(const uint8_t* d_root, const uint32_t* d_ntx, const uint8_t* d_bm, uint32_t n,

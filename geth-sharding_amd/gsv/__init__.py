@@ -642,6 +642,44 @@ def _ecrecover_precompile_batch_dev(self, in_t, out_t, ok_t, stream=None):
     check(_lib.load().gsv_ecrecover_precompile_batch_dev(self._h, _tptr(in_t), n, _tptr(out_t), _tptr(ok_t), sp))
 
 
+def _bn256_g1_batch(self, fn, inputs):
+    n = len(inputs)
+    out = np.zeros((n, 64), np.uint8)
+    st = np.zeros(n, np.uint8)
+    if n == 0:
+        return out, st
+    flat, off = _pack(inputs)
+    check(fn(self._h, _ptr(flat), _ptr(off), n, _ptr(out), _ptr(st)))
+    return out, st
+
+
+def _bn256_add_batch(self, inputs):
+    """The bn256Add precompile's Run over many inputs (core/vm/contracts.go:274-289): returns
+    (out64 (n,64), status (n,)); status[i] == ST_BN_BAD_INPUT (and a zero row) where the reference
+    returns the unmarshal error."""
+    return _bn256_g1_batch(self, _lib.load().gsv_bn256_add_batch, inputs)
+
+
+def _bn256_scalar_mul_batch(self, inputs):
+    """The bn256ScalarMul precompile's Run over many inputs (core/vm/contracts.go:297-312): returns
+    (out64 (n,64), status (n,)) as bn256_add_batch does."""
+    return _bn256_g1_batch(self, _lib.load().gsv_bn256_scalar_mul_batch, inputs)
+
+
+def _bn256_add_batch_dev(self, in_t, out_t, st_t, stream=None):
+    """in_t: torch uint8 CUDA tensor (n, 128) of right-padded records; out_t (n, 64), st_t (n,)."""
+    n = in_t.shape[0]
+    sp = _sp(stream)
+    check(_lib.load().gsv_bn256_add_batch_dev(self._h, _tptr(in_t), n, _tptr(out_t), _tptr(st_t), sp))
+
+
+def _bn256_scalar_mul_batch_dev(self, in_t, out_t, st_t, stream=None):
+    """in_t: torch uint8 CUDA tensor (n, 96) of right-padded records; out_t (n, 64), st_t (n,)."""
+    n = in_t.shape[0]
+    sp = _sp(stream)
+    check(_lib.load().gsv_bn256_scalar_mul_batch_dev(self._h, _tptr(in_t), n, _tptr(out_t), _tptr(st_t), sp))
+
+
 def _prepared_shapes(self):
     cnt = ctypes.c_size_t()
     nb = ctypes.c_size_t()
@@ -652,3 +690,7 @@ def _prepared_shapes(self):
 Context.ecrecover_precompile_batch = _ecrecover_precompile_batch
 Context.ecrecover_precompile_batch_dev = _ecrecover_precompile_batch_dev
 Context.prepared_shapes = _prepared_shapes
+Context.bn256_add_batch = _bn256_add_batch
+Context.bn256_scalar_mul_batch = _bn256_scalar_mul_batch
+Context.bn256_add_batch_dev = _bn256_add_batch_dev
+Context.bn256_scalar_mul_batch_dev = _bn256_scalar_mul_batch_dev

@@ -45,6 +45,7 @@ K_BN_FINAL = 7
 K_NOTARY = 8
 K_DERIVE_LEAF = 9
 K_HEADER = 10
+K_BN_G1 = 11
 
 # API errors (negative return values)
 E_INVALID_ARG = -1
@@ -107,6 +108,10 @@ SIGNATURES = [
     ("gsv_ctx_stream_count", ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     ("gsv_ecrecover_precompile_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
     ("gsv_ecrecover_precompile_batch_dev", ctypes.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    ("gsv_bn256_add_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    ("gsv_bn256_add_batch_dev", ctypes.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    ("gsv_bn256_scalar_mul_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    ("gsv_bn256_scalar_mul_batch_dev", ctypes.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
     ("gsv_chunk_root_prepare", ctypes.c_int, [_vp, _vp, _sz]),
     ("gsv_bn256_pairing_prepare", ctypes.c_int, [_vp, _vp, _sz]),
     ("gsv_notary_prepare", ctypes.c_int, [_vp, _vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_uint32]),

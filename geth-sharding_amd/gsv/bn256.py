@@ -4,6 +4,9 @@
     PairingCheckBatch(inputs)   the batch form: one verdict per precompile input
     Bn256Pairing.Run(input)     core/vm/contracts.go:333-360 (true32Byte / false32Byte / error)
 
+    G1Add(a, b) / G1ScalarMult(a, k)   cloudflare/bn256.go:62-78 over 64-byte encodings
+    Bn256Add.Run / Bn256ScalarMul.Run  core/vm/contracts.go:274-312 (64 bytes / error)
+
 Points use the precompile encoding: G1 = x || y, G2 = x.imag || x.real || y.imag || y.real,
 32-byte big-endian words (bn256.go:120-164, :256-306).  Malformed points raise
 ErrMalformedPoint where the reference's Unmarshal returns an error.
@@ -58,3 +61,43 @@ class Bn256Pairing:
         if v == _lib.PAIRING_BAD_INPUT:  # newCurvePoint / newTwistPoint error (contracts.go:344-351)
             raise ErrMalformedPoint("bn256: malformed point")
         return TRUE32 if v == _lib.PAIRING_TRUE else FALSE32
+
+
+def G1Add(a: bytes, b: bytes, ctx=None) -> bytes:
+    """Marshal(Unmarshal(a) + Unmarshal(b)) over 64-byte G1 encodings (bn256.go:62-67)."""
+    return Bn256Add().Run(bytes(a).ljust(64, b"\0")[:64] + bytes(b), ctx)
+
+
+def G1ScalarMult(a: bytes, k: int, ctx=None) -> bytes:
+    """Marshal(k * Unmarshal(a)) (bn256.go:70-78); k is taken mod 2^256 as the precompile's word."""
+    return Bn256ScalarMul().Run(bytes(a).ljust(64, b"\0")[:64] + (int(k) % 2**256).to_bytes(32, "big"), ctx)
+
+
+class Bn256Add:
+    """PrecompiledContract{RequiredGas, Run} for address 0x06 (core/vm/contracts.go:266-289)."""
+
+    GAS = 500  # params.Bn256AddGas (params/protocol_params.go:76)
+
+    def RequiredGas(self, input: bytes) -> int:
+        return self.GAS
+
+    def Run(self, input: bytes, ctx=None) -> bytes:
+        out, st = (ctx or default_context()).bn256_add_batch([bytes(input)])
+        if st[0] != _lib.ST_OK:  # newCurvePoint error (contracts.go:276-283)
+            raise ErrMalformedPoint("bn256: malformed point")
+        return out[0].tobytes()
+
+
+class Bn256ScalarMul:
+    """PrecompiledContract{RequiredGas, Run} for address 0x07 (core/vm/contracts.go:291-312)."""
+
+    GAS = 40000  # params.Bn256ScalarMulGas (params/protocol_params.go:77)
+
+    def RequiredGas(self, input: bytes) -> int:
+        return self.GAS
+
+    def Run(self, input: bytes, ctx=None) -> bytes:
+        out, st = (ctx or default_context()).bn256_scalar_mul_batch([bytes(input)])
+        if st[0] != _lib.ST_OK:  # newCurvePoint error (contracts.go:299-303)
+            raise ErrMalformedPoint("bn256: malformed point")
+        return out[0].tobytes()

@@ -29,6 +29,10 @@
  *                                 smc_client.go:245-248, signed at sharding/proposer/proposer.go:83)
  *
  *   gsv_ecrecover_precompile_batch <- the ecrecover precompile's Run (core/vm/contracts.go:78-101)
+ *   gsv_bn256_add_batch        <- the bn256Add precompile's Run (core/vm/contracts.go:274-289)
+ *                                 = G1.Unmarshal x 2, G1.Add, G1.Marshal (crypto/bn256/cloudflare/bn256.go:62-67)
+ *   gsv_bn256_scalar_mul_batch <- the bn256ScalarMul precompile's Run (core/vm/contracts.go:297-312)
+ *                                 = G1.Unmarshal, G1.ScalarMult, G1.Marshal (bn256.go:70-78)
  *
  * Conventions
  *   - Return value: GSV_SUCCESS (0) or a negative GSV_E_* API/HIP error. A bad ITEM never fails
@@ -123,6 +127,7 @@ int gsv_ctx_set_timing(gsv_ctx *ctx, int enable);
 #define GSV_K_NOTARY 8     /* blob index + per-tx decode/sighash/recover of the notary path */
 #define GSV_K_DERIVE_LEAF 9 /* generic DeriveSha leaf encode + hash */
 #define GSV_K_HEADER 10    /* collation header hashing + signer comparison */
+#define GSV_K_BN_G1 11     /* bn256Add / bn256ScalarMul: one launch per call */
 #define GSV_K_COUNT 12
 /* total milliseconds and launch count accumulated for kernel `kid` since the last reset */
 int gsv_ctx_kernel_time(gsv_ctx *ctx, int kid, double *total_ms, long *launches);
@@ -230,6 +235,27 @@ int gsv_bn256_pairing_check_batch(gsv_ctx *ctx, const uint8_t *in, const uint64_
 int gsv_bn256_pairing_prepare(gsv_ctx *ctx, const uint64_t *h_off, size_t n);
 int gsv_bn256_pairing_check_batch_dev(gsv_ctx *ctx, const uint8_t *d_in, const uint64_t *h_off, size_t n,
                                       uint8_t *d_verdict, void *stream);
+
+/* ---- BN254 G1 addition and scalar multiplication: the bn256Add (0x06) and bn256ScalarMul (0x07)
+ * precompiles (core/vm/contracts.go:274-312) ----
+ * Input i = in[off[i] .. off[i+1]), right-padded with zeros to the record size and cut there (getData,
+ * core/vm/common.go:37-47): add = x1 || y1 || x2 || y2 (128 B), scalar mul = x || y || k (96 B), 32-byte
+ * big-endian words.  A point decodes as G1.Unmarshal does (bn256.go:120-158): every coordinate < p (a
+ * coordinate equal to p is an error), (0, 0) is the point at infinity, anything else must satisfy
+ * y^2 = x^3 + 3.  status[i] = GSV_ST_BN_BAD_INPUT and 64 zero bytes where the reference returns the
+ * unmarshal error (whatever k is); else GSV_ST_OK and out64[i] = Marshal(P1 + P2) / Marshal(k P) for any
+ * k in [0, 2^256): the affine point, 64 zero bytes for infinity.  So an empty input is OK with 64 zero
+ * bytes.  No prepare call. */
+int gsv_bn256_add_batch(gsv_ctx *ctx, const uint8_t *in, const uint64_t *off, size_t n, uint8_t *out64,
+                        uint8_t *status);
+int gsv_bn256_scalar_mul_batch(gsv_ctx *ctx, const uint8_t *in, const uint64_t *off, size_t n, uint8_t *out64,
+                               uint8_t *status);
+/* Device-resident forms over padded records: d_in128 = n x 128 B, d_in96 = n x 96 B in HBM; d_out64 =
+ * n x 64 B, d_status = n bytes.  They only enqueue (one launch) on `stream` (NULL = the context stream). */
+int gsv_bn256_add_batch_dev(gsv_ctx *ctx, const uint8_t *d_in128, size_t n, uint8_t *d_out64, uint8_t *d_status,
+                            void *stream);
+int gsv_bn256_scalar_mul_batch_dev(gsv_ctx *ctx, const uint8_t *d_in96, size_t n, uint8_t *d_out64,
+                                   uint8_t *d_status, void *stream);
 
 /* ---- synthetic signed workload (bench / test data generator; signing is not on the path) ----
  * key_i, msg_i, nonce_i = Keccak256(le64(seed) || le64(i) || "key"/"msg"/"nce"), key and nonce

@@ -1,5 +1,5 @@
 """Operation counts of OUR kernels per unit of work, from the instrumented build
-(geth-sharding_amd/csrc/opcount.cuh; built by `VSRCS="ecrecover bn256 notary collation"
+(geth-sharding_amd/csrc/opcount.cuh; built by `VSRCS="ecrecover bn256 bn_g1 notary collation"
 tools/build_variant.sh opcount -DGSV_OPCOUNT`), at the bench's batch sizes:
 
     recovery       one k_ecrecover lane of the configs[1] batch (2^20 signatures)
@@ -7,6 +7,9 @@ tools/build_variant.sh opcount -DGSV_OPCOUNT`), at the bench's batch sizes:
                    per-rank batch at N = 8 (8,192 checks: another lane layout, §3.4 of DESIGN.md)
     notary_tx      one transaction of the configs[3] step (100 shards x 8,192 txs through k_notary_tx:
                    RLP decode, sighash, recovery, address; every 128th tx invalid by construction)
+    bn256_scalar_mul / bn256_scalar_mul_bitserial / bn256_add
+                   one item of a 65,536-item batch of the G1 precompiles (k_bn_g1_mul in its GLV and
+                   bit-serial forms, k_bn_g1_add): points s_i G, scalars uniform over 256 bits
 
 "mad" is the number of v_mad_u64_u32 (32 x 32 -> 64-bit multiply-adds: the unit of the VALU MAC
 roofline) our kernels execute, from the op counts and each op's mad count in our limb layout:
@@ -107,6 +110,36 @@ def main():
     c = per_unit(read("notary"), nsh * txs)
     c["mac_equiv"] = round(sum(W[k] * c.get(k, 0) for k in ("fe_mul", "fe_sqr", "sc_mul", "sc_sqr", "fe_dot")), 1)
     out["notary_tx"] = c
+    # ---- the G1 precompiles: both multiplication forms and the addition
+    n = 65536
+    rng = np.random.default_rng(2026)
+    g = torch.zeros((n, 64), dtype=torch.uint8, device=dev)
+    g[:, 31] = 1
+    g[:, 63] = 2
+    pts = torch.empty((n, 64), dtype=torch.uint8, device=dev)
+    res = torch.empty((n, 64), dtype=torch.uint8, device=dev)
+    gst = torch.empty((n,), dtype=torch.uint8, device=dev)
+    ctx.bn256_scalar_mul_batch_dev(torch.cat([g, torch.from_numpy(rng.integers(0, 256, (n, 32), dtype=np.uint8))
+                                              .to(dev)], dim=1).contiguous(), pts, gst)
+    rec = torch.cat([pts, torch.from_numpy(rng.integers(0, 256, (n, 32), dtype=np.uint8)).to(dev)], dim=1).contiguous()
+    torch.cuda.synchronize()
+    read("bn_g1")  # drop the point generation's counts
+    for name, env in (("bn256_scalar_mul", None), ("bn256_scalar_mul_bitserial", "1")):
+        if env:
+            os.environ["GSV_BN_G1_BITSERIAL"] = env
+        ctx.bn256_scalar_mul_batch_dev(rec, res, gst)
+        torch.cuda.synchronize()
+        os.environ.pop("GSV_BN_G1_BITSERIAL", None)
+        assert int(gst.max()) == 0
+        c = per_unit(read("bn_g1"), n)
+        c["mac_equiv"] = round(W["bn_mul"] * c.get("bn_mul", 0) + W["bn_redc"] * c.get("bn_redc", 0), 1)
+        out[name] = c
+    ctx.bn256_add_batch_dev(torch.cat([pts, torch.roll(pts, 1, 0)], dim=1).contiguous(), res, gst)
+    torch.cuda.synchronize()
+    assert int(gst.max()) == 0
+    c = per_unit(read("bn_g1"), n)
+    c["mac_equiv"] = round(W["bn_mul"] * c.get("bn_mul", 0) + W["bn_redc"] * c.get("bn_redc", 0), 1)
+    out["bn256_add"] = c
     json.dump(out, sys.stdout, indent=1)
     print()
 
