@@ -25,7 +25,7 @@ hipError_t launch_keccak256(const uint8_t* data, const uint64_t* off, uint32_t n
 
 // Launchers call timer_begin(tctx, GSV_HOOK_TAIL) (no launch follows it directly) where the call's
 // bulk kernels end and its latency-bound tail begins (trie top, Miller loop + final exponentiation):
-// with pipelined shape instances the next call's bulk kernels start there (gsv_api.hip shape_run).
+// with pipelined shape instances the next call's bulk kernels start there (gsv_ctx.h shape_run).
 constexpr int GSV_HOOK_TAIL = -1;
 
 // chunk_root.hip

@@ -1,0 +1,144 @@
+// Size arithmetic of one device allocation, free of HIP (plain C++17; tests/native/staging_host.cpp
+// compiles it with g++).  A Layout collects 256-B aligned regions first and is bound to memory
+// afterwards: a prepared shape's workspace (Shape::at) and the buffers a host-pointer entry point
+// stages in the context's arena.  Every staged buffer is declared once, in the *Stage struct of its
+// entry point; the total to reserve is the Layout's `n` after those declarations, and a pointer exists
+// only once the arena is reserved (arena_reserve may move it): buf(c->arena).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+namespace gsv {
+namespace api {
+
+inline size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
+
+constexpr size_t kAbsent = ~(size_t)0;
+
+// a staged buffer: its offset in the allocation, or absent (an optional output the caller did not ask
+// for: reserves nothing, binds to nullptr)
+template <typename T>
+struct Buf {
+    size_t off = kAbsent, bytes = 0;
+    T* operator()(uint8_t* base) const { return off == kAbsent ? nullptr : (T*)(base + off); }
+};
+
+// regions of one device allocation (256-B aligned offsets; a zero-length region still gets 256 B, so
+// no two regions share an address)
+struct Layout {
+    size_t n = 0;
+    size_t add(size_t bytes) {
+        size_t o = n;
+        n += al(bytes ? bytes : 1);
+        return o;
+    }
+    template <typename T = uint8_t>
+    Buf<T> buf(size_t bytes, bool present = true) {
+        return present ? Buf<T>{add(bytes), bytes} : Buf<T>{};
+    }
+};
+
+using B8 = Buf<uint8_t>;
+
+// ---- the staged buffers of the host-pointer entry points (in arena order)
+struct KeccakStage {  // gsv_keccak256_batch
+    B8 data;
+    Buf<uint64_t> off;
+    B8 out;
+    KeccakStage(Layout& L, size_t bytes, size_t n)
+        : data(L.buf(bytes + 8)), off(L.buf<uint64_t>((n + 1) * 8)), out(L.buf(n * 32)) {}
+};
+struct EcrecoverStage {  // gsv_ecrecover_batch
+    B8 msg, sig, pub, addr, st;
+    EcrecoverStage(Layout& L, size_t n, bool want_pub, bool want_addr)
+        : msg(L.buf(n * 32)), sig(L.buf(n * 65)), pub(L.buf(n * 65, want_pub)), addr(L.buf(n * 20, want_addr)),
+          st(L.buf(n)) {}
+};
+// fixed-size records in, fixed-size results and a status byte out: gsv_ecrecover_precompile_batch
+// (128 -> 32), bn_g1_host (128 or 96 -> 64)
+struct RecordStage {
+    B8 in, out, st;
+    RecordStage(Layout& L, size_t n, size_t rec, size_t res) : in(L.buf(n * rec)), out(L.buf(n * res)), st(L.buf(n)) {}
+};
+struct SenderStage {  // gsv_sender_batch, and the tail of tx_sender_impl
+    B8 h, r, s;
+    Buf<uint64_t> v;
+    B8 vb, a, st;
+    SenderStage(Layout& L, size_t n)
+        : h(L.buf(n * 32)), r(L.buf(n * 32)), s(L.buf(n * 32)), v(L.buf<uint64_t>(n * 8)), vb(L.buf(n)),
+          a(L.buf(n * 20)), st(L.buf(n)) {}
+};
+struct TxSenderStage {  // tx_sender_impl: the sighash preimages, then recoverPlain's buffers
+    B8 pre;
+    Buf<uint64_t> poff;
+    SenderStage snd;
+    TxSenderStage(Layout& L, size_t pbytes, size_t n)
+        : pre(L.buf(pbytes + 8)), poff(L.buf<uint64_t>((n + 1) * 8)), snd(L, n) {}
+};
+struct SynthSignStage {  // gsv_synth_sign
+    B8 msg, sig, pub, addr;
+    SynthSignStage(Layout& L, size_t n, bool want_pub, bool want_addr)
+        : msg(L.buf(n * 32)), sig(L.buf(n * 65)), pub(L.buf(n * 65, want_pub)), addr(L.buf(n * 20, want_addr)) {}
+};
+// `bytes` of bodies (16-byte aligned starts, stage_offsets) or list values in, a root per body or list
+// out: gsv_chunk_root_batch, gsv_collation_poc_batch, gsv_derive_sha_batch
+struct RootsStage {
+    B8 in, roots;
+    RootsStage(Layout& L, size_t bytes, size_t n) : in(L.buf(bytes + 16)), roots(L.buf(n * 32)) {}
+};
+struct PairingStage {  // gsv_bn256_pairing_check_batch
+    B8 in, verdict;
+    PairingStage(Layout& L, size_t bytes, size_t n) : in(L.buf(bytes + 8)), verdict(L.buf(n)) {}
+};
+// gsv_notary_validate_shards, and the rank's own block in gsv_notary_validate_partition
+struct NotaryStage {
+    B8 bodies, root;
+    Buf<uint32_t> ntx;
+    B8 bitmap, senders, status;
+    NotaryStage(Layout& L, size_t bytes, size_t n, uint32_t max_txs, bool want_senders, bool want_status)
+        : bodies(L.buf(bytes + 16)), root(L.buf(n * 32)), ntx(L.buf<uint32_t>(n * 4)),
+          bitmap(L.buf(n * ((max_txs + 7) / 8))), senders(L.buf(n * max_txs * 20, want_senders)),
+          status(L.buf(n * max_txs, want_status)) {}
+};
+
+// shard partition: rank r of N validates shards [first, first + n) of n_total; a block is a header
+// {int32 status, uint32 shards} + `per` records of R bytes
+struct PartDims {
+    size_t first, n, per, R, bm, B;
+};
+inline PartDims part_dims(size_t n_total, int N, int r, uint32_t max_txs) {
+    PartDims d;
+    d.first = n_total * (size_t)r / (size_t)N;
+    d.n = n_total * (size_t)(r + 1) / (size_t)N - d.first;
+    d.per = (n_total + N - 1) / N;
+    d.bm = (max_txs + 7) / 8;
+    d.R = (36 + d.bm + 7) / 8 * 8;  // root 32 | ntx 4 | bitmap, padded to 8 (gsv/shards.py)
+    d.B = 8 + d.per * d.R;          // header {int32 status, uint32 shards} + records
+    return d;
+}
+// gsv_notary_validate_partition: the rank's block, the gathered blocks, the gathered outputs and the
+// per-rank status words come FIRST (`gathered` = their end), so a rank whose own block failed reserves
+// only those and still joins the all-gather; the own block's buffers follow
+struct PartitionStage {
+    B8 blk, all, oroot;
+    Buf<uint32_t> ontx;
+    B8 obm;
+    Buf<int32_t> rst;
+    size_t gathered;
+    NotaryStage own;
+    PartitionStage(Layout& L, const PartDims& d, size_t n_total, int N, size_t bytes, uint32_t max_txs,
+                   bool want_senders, bool want_status)
+        : blk(L.buf(d.B)), all(L.buf((size_t)N * d.B)), oroot(L.buf(n_total * 32)),
+          ontx(L.buf<uint32_t>(n_total * 4)), obm(L.buf(n_total * d.bm)), rst(L.buf<int32_t>((size_t)N * 4)),
+          gathered(L.n), own(L, bytes, d.n, max_txs, want_senders, want_status) {}
+};
+struct HeaderStage {  // gsv_collation_header_verify_batch
+    B8 sid, root, per, prop, sig, nil, hash, signer, st, scr;
+    HeaderStage(Layout& L, size_t n, size_t scratch_bytes, bool has_nil, bool want_hash, bool want_signer)
+        : sid(L.buf(n * 32)), root(L.buf(n * 32)), per(L.buf(n * 32)), prop(L.buf(n * 20)), sig(L.buf(n * 65)),
+          nil(L.buf(n, has_nil)), hash(L.buf(n * 32, want_hash)), signer(L.buf(n * 20, want_signer)), st(L.buf(n)),
+          scr(L.buf(scratch_bytes)) {}
+};
+
+}  // namespace api
+}  // namespace gsv

@@ -154,6 +154,34 @@ def test_header_proposer_signatures(ctx):
             assert not signer[i].any()
 
 
+def test_header_host_path_optional_buffers_match_dev_path(ctx):
+    # the host path with nil_flags, hash32_out and signer20_out all absent (the wrapper always passes the
+    # outputs, so through the C ABI directly) and all present, against the prepared _dev path
+    import torch
+    from gsv import _lib, _ptr, check
+    cases = [c for c in golden("collation.json")["signed_headers"]
+             if c["chunk_root"] is not None and c["proposer"] is not None and c["sig"]][:3]
+    n = len(cases)
+    assert n == 3
+    sid, root, per, prop, sig, nil = _headers(cases)
+    assert not nil.any()
+    st0 = np.full(n, 0xEE, np.uint8)
+    check(_lib.load().gsv_collation_header_verify_batch(ctx._h, _ptr(sid), _ptr(root), _ptr(per), _ptr(prop), _ptr(sig),
+                                                        None, n, None, None, _ptr(st0)))
+    h1, signer1, st1 = ctx.collation_header_verify_batch(sid, root, per, prop, sig, nil)
+    dev = [torch.tensor(a, device="cuda") for a in (sid, root, per, prop, sig, nil)]
+    h2 = torch.zeros((n, 32), dtype=torch.uint8, device="cuda")
+    signer2 = torch.zeros((n, 20), dtype=torch.uint8, device="cuda")
+    st2 = torch.full((n,), 0xEE, dtype=torch.uint8, device="cuda")
+    ctx.collation_header_verify_batch_dev(*dev[:5], st2, nil_t=dev[5], hash_t=h2, signer_t=signer2)
+    torch.cuda.synchronize()
+    assert st0.tobytes() == st1.tobytes() == st2.cpu().numpy().tobytes()
+    assert h1.tobytes() == h2.cpu().numpy().tobytes()
+    assert signer1.tobytes() == signer2.cpu().numpy().tobytes()
+    for i, c in enumerate(cases):
+        assert bytes(h1[i]).hex() == c["hash"], i
+
+
 def test_sharding_mirror_api(ctx, oracle):
     from gsv import sharding as S
     c = golden("collation.json")["signed_headers"][0]
@@ -176,7 +204,7 @@ def test_sharding_mirror_api(ctx, oracle):
 
 def test_dev_calls_on_two_streams_share_the_workspace_safely(ctx, oracle):
     # *_dev calls return without a host sync; calls on different streams are ordered on the GPU
-    # through the context's workspace event (gsv_api.hip work_begin/work_end)
+    # through the prepared shape's per-instance event (csrc/gsv_ctx.h shape_run)
     import torch
     rng = np.random.default_rng(17)
     s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()

@@ -1,5 +1,5 @@
 #!/bin/bash
-# The notary pipeline's step mark (GSV_NOTARY_STAGGER, gsv_api.hip notary_run): 1 = the chunk root's
+# The notary pipeline's step mark (GSV_NOTARY_STAGGER, gsv_notary.hip notary_run): 1 = the chunk root's
 # (after its bottom level, r03-r05), 0 = none, 2 = after the blob index; 13 / 25 / 100 shards (N = 8 / 4 /
 # 1 rank shares of configs[3]) at depths 2-4, 12 and 40 steps per measurement, interleaved twice.  GPU box.
 set -u

@@ -2,20 +2,23 @@
 # Builds an A/B variant of libgsv.so with extra -D flags (sources in $VSRCS, default ecrecover notary)
 # into variants/<name>/ (git-ignored,
 # shipped to the GPU box); select it at run time with GSV_LIB_PATH=variants/<name>/libgsv.so.
+# The unit list, the compiler and the flags are the Makefile's (make -s print-SRCS ...).
 set -e
 name=$1; shift
 R=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p $R/variants/$name
 cd $R/geth-sharding_amd/csrc
 make -s -j8 >/dev/null
-pids=""
+HIPCC=$(make -s print-HIPCC); BASE=$(make -s print-BASE); LIBS=$(make -s print-LIBS)
 VSRCS=${VSRCS:-ecrecover notary}
 for f in $VSRCS; do
-    /opt/rocm/bin/hipcc "$@" -O3 -std=c++17 -fPIC --offload-arch=gfx950 -c $f.hip -o $R/variants/$name/$f.o 2>&1 | grep -v hip-link || true &
+    $HIPCC "$@" $BASE -c $f.hip -o $R/variants/$name/$f.o 2>&1 | grep -v hip-link || true &
 done
 wait
-for f in gsv_api keccak ecrecover chunk_root tx_host bn256 bn_g1 notary collation; do
+objs=""
+for f in $(make -s print-SRCS | sed 's/\.hip//g'); do
     case " $VSRCS " in *" $f "*) ;; *) cp build/$f.o $R/variants/$name/ ;; esac
+    objs="$objs $R/variants/$name/$f.o"
 done
-/opt/rocm/bin/hipcc -fPIC --offload-arch=gfx950 -shared -o $R/variants/$name/libgsv.so $R/variants/$name/*.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+$HIPCC $BASE -shared -o $R/variants/$name/libgsv.so $objs $LIBS
 echo built $R/variants/$name/libgsv.so
