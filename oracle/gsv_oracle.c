@@ -403,6 +403,106 @@ void oracle_ecrecover_batch(const uint8_t *msg32, const uint8_t *sig65, long n, 
     for (int t = 0; t < threads; t++) pthread_join(th[t], NULL);
 }
 
+/* ===================================================================================
+ * Chain check: Q[i] == Q[i-1] + B for a run of affine points, without inversions.
+ * With (x1, y1) = Q[i-1], (x2, y2) = B, (x3, y3) = Q[i] and x1 != x2 the chord law
+ *   l = (y2 - y1) / (x2 - x1),  x3 = l^2 - x1 - x2,  y3 = l (x1 - x3) - y1
+ * holds iff the two cross-multiplied equations
+ *   (x3 + x1 + x2) (x2 - x1)^2 == (y2 - y1)^2
+ *   (y3 + y1) (x2 - x1)        == (y2 - y1) (x1 - x3)
+ * do.  Every point must also have coordinates < p and lie on y^2 = x^3 + 7.
+ * Used by the test that sweeps every entry of the GPU's fixed-base table.
+ * =================================================================================== */
+static int affine_on_curve(u256 *x, u256 *y, const uint8_t *p64) {
+    u256 l, r, seven = {{7, 0, 0, 0}};
+    u256_from_be(x, p64);
+    u256_from_be(y, p64 + 32);
+    if (u256_cmp(x, &SECP_P) >= 0 || u256_cmp(y, &SECP_P) >= 0) return 0;
+    FMUL(&l, y, y);
+    FMUL(&r, x, x);
+    FMUL(&r, &r, x);
+    FADD(&r, &r, &seven);
+    return u256_cmp(&l, &r) == 0;
+}
+
+typedef struct {
+    const uint8_t *q;
+    u256 bx, by;
+    long lo, hi;
+    long first_bad; /* lowest failing index in [lo, hi), or -1 */
+    int degenerate; /* some x(Q[i-1]) == x(B) */
+} chain_job;
+
+static void *chain_worker(void *arg) {
+    chain_job *j = (chain_job *)arg;
+    j->first_bad = -1;
+    j->degenerate = 0;
+    u256 x1, y1, x3, y3;
+    int prev_ok = 0;
+    if (j->lo > 0) prev_ok = affine_on_curve(&x1, &y1, j->q + 64 * (j->lo - 1));
+    for (long i = j->lo; i < j->hi; i++) {
+        int on = affine_on_curve(&x3, &y3, j->q + 64 * i), ok = on;
+        if (ok && i > 0) {
+            /* a bad predecessor is reported at its own index (by this worker or the one before) */
+            if (prev_ok) {
+                u256 dx, dy, dx2, sum, l, r, t;
+                FSUB(&dx, &j->bx, &x1);
+                FSUB(&dy, &j->by, &y1);
+                if (u256_is_zero(&dx)) {
+                    j->degenerate = 1;
+                } else {
+                    FMUL(&dx2, &dx, &dx);
+                    FADD(&sum, &x3, &x1);
+                    FADD(&sum, &sum, &j->bx);
+                    FMUL(&l, &sum, &dx2);
+                    FMUL(&r, &dy, &dy);
+                    if (u256_cmp(&l, &r) != 0) ok = 0;
+                    FADD(&t, &y3, &y1);
+                    FMUL(&l, &t, &dx);
+                    FSUB(&t, &x1, &x3);
+                    FMUL(&r, &dy, &t);
+                    if (u256_cmp(&l, &r) != 0) ok = 0;
+                }
+            }
+        }
+        if (!ok && j->first_bad < 0) j->first_bad = i;
+        /* after a point that is on the curve but off the chain, the chain is judged from that point on */
+        prev_ok = on;
+        x1 = x3;
+        y1 = y3;
+    }
+    return NULL;
+}
+
+/* Returns -1 when every Q[i] (n affine points X || Y, big-endian) is a curve point with
+ * coordinates < p and Q[i] == Q[i-1] + B for all i >= 1; otherwise the first index that fails
+ * (an index i >= 1 whose predecessor is itself no curve point is not judged: the predecessor is
+ * the one reported; 0 means Q[0] is no curve point).  OR_CHAIN_DEGENERATE when some
+ * x(Q[i-1]) == x(B) (the chord equations say nothing there), OR_CHAIN_BAD_BASE when B is no
+ * curve point. */
+long oracle_secp_chain_check(const uint8_t *q64, long n, const uint8_t base64[64], int threads) {
+    if (threads < 1) threads = 1;
+    if (threads > 256) threads = 256;
+    if (n < threads) threads = n > 0 ? (int)n : 1;
+    u256 bx, by;
+    if (!affine_on_curve(&bx, &by, base64)) return OR_CHAIN_BAD_BASE;
+    pthread_t th[256];
+    chain_job jobs[256];
+    for (int t = 0; t < threads; t++) {
+        jobs[t] = (chain_job){q64, bx, by, n * t / threads, n * (t + 1) / threads, -1, 0};
+        pthread_create(&th[t], NULL, chain_worker, &jobs[t]);
+    }
+    long bad = -1;
+    int degenerate = 0;
+    for (int t = 0; t < threads; t++) {
+        pthread_join(th[t], NULL);
+        if (jobs[t].degenerate) degenerate = 1;
+        if (bad < 0 && jobs[t].first_bad >= 0) bad = jobs[t].first_bad;
+    }
+    if (degenerate) return OR_CHAIN_DEGENERATE;
+    return bad;
+}
+
 /* Key generation / signing: fixture generation only (signing is not on the path). */
 int oracle_secp_pubkey(uint8_t pub65[65], const uint8_t seckey[32]) {
     u256 d;

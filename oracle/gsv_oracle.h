@@ -26,6 +26,8 @@ enum {
     OR_BAD_RLP = 8,
     OR_BN_BAD_INPUT = 9,
 };
+/* oracle_secp_chain_check results below -1 (-1 = the chain holds, >= 0 = first failing index) */
+enum { OR_CHAIN_DEGENERATE = -2, OR_CHAIN_BAD_BASE = -3 };
 
 void oracle_keccak256(const uint8_t *in, size_t len, uint8_t out[32]);
 void oracle_keccak256_batch(const uint8_t *data, const uint64_t *off, long n, uint8_t *out32);
@@ -36,6 +38,9 @@ void oracle_keccak_sponge(const uint8_t *in, size_t len, int rate, uint8_t dsbyt
 int oracle_ecrecover(uint8_t pub65[65], const uint8_t sig65[65], const uint8_t msg32[32]);
 void oracle_ecrecover_batch(const uint8_t *msg32, const uint8_t *sig65, long n, uint8_t *pub65,
                             uint8_t *status, int threads);
+/* first i with Q[i] != Q[i-1] + B or Q[i] no curve point (n affine points X || Y, big-endian), -1 if
+ * none; no inversions (cross-multiplied chord equations) */
+long oracle_secp_chain_check(const uint8_t *q64, long n, const uint8_t base64[64], int threads);
 int oracle_recover_plain(uint8_t addr20[20], const uint8_t sighash[32], const uint8_t *r, size_t rlen,
                          const uint8_t *s, size_t slen, const uint8_t *v, size_t vlen, int homestead);
 int oracle_tx_sender(uint8_t addr20[20], const uint8_t *rlp, size_t len, const uint8_t *chain_id,

@@ -45,6 +45,8 @@ def lib():
                                            ctypes.c_uint8, ctypes.c_char_p, ctypes.c_size_t]
         L.oracle_ecrecover.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
         L.oracle_ecrecover_batch.argtypes = [c_u8p, c_u8p, ctypes.c_long, c_u8p, c_u8p, ctypes.c_int]
+        L.oracle_secp_chain_check.argtypes = [c_u8p, ctypes.c_long, ctypes.c_char_p, ctypes.c_int]
+        L.oracle_secp_chain_check.restype = ctypes.c_long
         L.oracle_tx_sender.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t,
                                        ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int]
         L.oracle_tx_sighash.argtypes = L.oracle_tx_sender.argtypes
@@ -121,6 +123,18 @@ def ecrecover_batch(msgs: np.ndarray, sigs: np.ndarray, threads: int = 8):
     st = np.zeros(n, np.uint8)
     lib().oracle_ecrecover_batch(_ptr(msgs), _ptr(sigs), n, _ptr(pub), _ptr(st), threads)
     return pub, st
+
+
+CHAIN_OK, CHAIN_DEGENERATE, CHAIN_BAD_BASE = -1, -2, -3
+
+
+def secp_chain_check(points: np.ndarray, base64: bytes, threads: int = 8) -> int:
+    """points (n, 64) uint8, affine X || Y big-endian.  CHAIN_OK when every row is a curve point and
+    row i == row i-1 + base for all i >= 1, else the first row that fails (no inversions: the chord
+    equations cross-multiplied); CHAIN_DEGENERATE when some row shares its x with the base."""
+    points = np.ascontiguousarray(points, dtype=np.uint8).reshape(-1, 64)
+    assert len(base64) == 64
+    return int(lib().oracle_secp_chain_check(_ptr(points), points.shape[0], bytes(base64), threads))
 
 
 def tx_sender(rlp: bytes, chain_id: int = 1, signer: int = 0):
