@@ -17,7 +17,10 @@
 //     LDS of two waves per SIMD holds four), built on an isomorphic curve
 //     (libsecp-style "global z") so all table points are affine without an inversion; the lambda
 //     half uses (beta x, y).  128 doublings + 65 mixed additions (w = 3 with the 4-entry table in
-//     LDS: 129 + 88, measured 6 % slower: 15.5 -> 14.5 ms per 2^20 recoveries).
+//     LDS: 129 + 88, measured 6 % slower: 15.5 -> 14.5 ms per 2^20 recoveries).  The accumulator
+//     carries (X, W = 2Y, Z) and a doubling returns -2P with six reductions instead of seven
+//     (secp256k1_fe9.cuh gejw_dbl_neg: 3 X^2 as one squaring, -W3 = E 2(X3 - D) + B^2 as one
+//     product-plus-square); four doublings between adds restore the sign.
 //   * u1*G: fixed-base comb, 13 windows of 20 bits from a 1.09 GB affine table in HBM (one random
 //     80-byte entry per window, prefetched a window ahead), 12 mixed additions (window 0 starts the sum), no doublings
 //     (gsv_internal.h COMB_BITS; 16-bit windows from the Infinity Cache were 1.3 % slower).

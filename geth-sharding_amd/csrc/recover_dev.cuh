@@ -4,9 +4,15 @@
 #include "gsv_internal.h"
 #include "keccak_dev.cuh"
 #include "secp256k1_dev.cuh"
-// the rare p == q doubling of the mixed add runs out of line (see gej9_dbl_ool below)
-namespace gsv { struct gej9; __device__ void gej9_dbl_rare(gej9& o, const gej9& p); }
+// the rare p == q doubling of the mixed add runs out of line (see gej9_dbl_ool below), in the
+// Jacobian and in the W convention
+namespace gsv {
+struct gej9;
+__device__ void gej9_dbl_rare(gej9& o, const gej9& p);
+__device__ void gejw_dbl_rare(gej9& o, const gej9& p);
+}
 #define GEJ9_DBL_RARE(o, p) gej9_dbl_rare(o, p)
+#define GEJW_DBL_RARE(o, p) gejw_dbl_rare(o, p)
 #include "secp256k1_fe9.cuh"
 #include "modinv30.cuh"
 
@@ -37,6 +43,8 @@ __device__ constexpr uint32_t HALF_N[8] = {0x681B20A0u, 0xDFE92F46u, 0x57A4501Du
 // {+-1, +-3, ..., +-(2^W - 1)}, a table of the 2^(W-1) odd multiples of R, W doublings per digit.
 // (w = 5 measured slower, r02-r05: DESIGN.md §7.3)
 constexpr int GLV_W = 4;
+// the ladder's doubling returns -2P (gejw_dbl_neg): the sign is back to + after an even run
+static_assert(GLV_W % 2 == 0, "an odd run of negating doublings leaves the accumulator at -2^W P");
 constexpr int GLV_NT = 1 << (GLV_W - 1);             // table entries
 constexpr int GLV_DIGITS = (130 + GLV_W - 1) / GLV_W;  // |k| < 2^130: the split gives < 2^128, + a lattice vector (glv_make_odd) < 2^129.3
 // digit code = sign bit above a (W - 1)-bit table index, packed in DIG_SLOT-bit slots
@@ -164,6 +172,7 @@ GSV_DI void ge9_cmov(ge9& r, const ge9& a, bool f) {
 // in I-cache; the point travels in VGPR vectors (an aggregate or pointer argument would pin the
 // caller's accumulator to scratch memory).
 typedef uint32_t gsv_v32 __attribute__((ext_vector_type(32)));
+template <bool WCONV>
 __device__ __noinline__ gsv_v32 gej9_dbl_ool(gsv_v32 in) {
     gej9 p, d;
 #pragma unroll
@@ -172,7 +181,8 @@ __device__ __noinline__ gsv_v32 gej9_dbl_ool(gsv_v32 in) {
         p.y.v[i] = in[9 + i];
         p.z.v[i] = in[18 + i];
     }
-    gej9_dbl(d, p);
+    if (WCONV) gejw_dbl(d, p);
+    else gej9_dbl(d, p);
     gsv_v32 o;
 #pragma unroll
     for (int i = 0; i < 9; i++) {
@@ -184,7 +194,8 @@ __device__ __noinline__ gsv_v32 gej9_dbl_ool(gsv_v32 in) {
     for (int i = 27; i < 32; i++) o[i] = 0;
     return o;
 }
-__device__ void gej9_dbl_rare(gej9& o, const gej9& p) {
+template <bool WCONV>
+GSV_DI void gej9_dbl_rare_call(gej9& o, const gej9& p) {
     gsv_v32 in;
 #pragma unroll
     for (int i = 0; i < 9; i++) {
@@ -194,7 +205,7 @@ __device__ void gej9_dbl_rare(gej9& o, const gej9& p) {
     }
 #pragma unroll
     for (int i = 27; i < 32; i++) in[i] = 0;
-    gsv_v32 d = gej9_dbl_ool(in);
+    gsv_v32 d = gej9_dbl_ool<WCONV>(in);
 #pragma unroll
     for (int i = 0; i < 9; i++) {
         o.x.v[i] = d[i];
@@ -202,6 +213,8 @@ __device__ void gej9_dbl_rare(gej9& o, const gej9& p) {
         o.z.v[i] = d[18 + i];
     }
 }
+__device__ void gej9_dbl_rare(gej9& o, const gej9& p) { gej9_dbl_rare_call<false>(o, p); }
+__device__ void gejw_dbl_rare(gej9& o, const gej9& p) { gej9_dbl_rare_call<true>(o, p); }
 
 GSV_DI void table_select9(ge9& out, const ge9 T[4], uint32_t idx) {
     out = T[0];
@@ -233,7 +246,9 @@ GSV_DI void comb_shift(uint32_t c[8]) {
     for (int i = 0; i < 7; i++) c[i] = __builtin_amdgcn_alignbit(c[i + 1], c[i], COMB_BITS);
     c[7] >>= COMB_BITS;
 }
-// u*G with the fixed-base comb table (COMB_WINDOWS mixed adds, no doublings).  The windows' digits are
+// u*G with the fixed-base comb table (COMB_WINDOWS mixed adds, no doublings), summed in the W
+// convention (the mixed add it shares with the GLV ladder) and returned Jacobian, Z magnitude 2.
+// The windows' digits are
 // read from the bottom of a copy of u shifted by COMB_BITS per window (r05): comb_digit's word select
 // with a loop-variant index was turned into a private array written to scratch and read back by a
 // dynamic offset twice per window (72 bytes of scratch stores per window, ~0.8 KB per recovery; r04's
@@ -246,7 +261,7 @@ GSV_DI void comb_mul_g9(gej9& acc, bool& inf, const sc& u, const uint4* __restri
     gtab_load(Pn, gtab + (size_t)d0 * GTAB_ENTRY_U4);
     // window 0 starts the sum: its entry is the accumulator (Z = 1), no add
     acc.x = Pn.x;
-    acc.y = Pn.y;
+    fe9_add(acc.y, Pn.y, Pn.y);  // W = 2y, 2
     fe9_set_u32(acc.z, 1);
     inf = d0 == 0;
     comb_shift(c);  // c = u >> (COMB_BITS w) at the top of window w
@@ -261,12 +276,13 @@ GSV_DI void comb_mul_g9(gej9& acc, bool& inf, const sc& u, const uint4* __restri
         }
         gej9 t;
         bool tinf = inf;
-        gej9_add_ge(t, tinf, acc, P);
+        gejw_add_ge(t, tinf, acc, P);
         if (d != 0) {
             acc = t;
             inf = tinf;
         }
     }
+    gejw_to_gej9(acc, acc);
 }
 
 // Jacobian -> affine canonical 8 x 32-bit words
@@ -571,7 +587,7 @@ GSV_DI uint32_t recover_core(fe& qx, fe& qy, const uint32_t msg[8], const uint32
         fe9_mul(zfac, f, zd);  // f = all the z-ratios: the entries' common Z on E is zd f
     }
 
-    gej9 acc;
+    gej9 acc;  // W convention (X, 2Y, Z) through the ladder
     bool ainf = true;
 #pragma unroll
     for (int k = 0; k < 9; k++) {
@@ -583,7 +599,7 @@ GSV_DI uint32_t recover_core(fe& qx, fe& qy, const uint32_t msg[8], const uint32
     for (int i = GLV_DIGITS - 1; i >= 0; i--) {
         if (i != GLV_DIGITS - 1) {
 #pragma unroll 1
-            for (int d = 0; d < GLV_W; d++) gej9_dbl(acc, acc);
+            for (int d = 0; d < GLV_W; d++) gejw_dbl_neg(acc, acc);  // -2P each: + again after GLV_W
         }
         constexpr uint32_t CMASK = (1u << DIG_SLOT) - 1u;
         uint32_t c1 = (sel_word(dig1, (uint32_t)i / DIG_PER_WORD) >> ((i % DIG_PER_WORD) * DIG_SLOT)) & CMASK;
@@ -620,15 +636,16 @@ GSV_DI uint32_t recover_core(fe& qx, fe& qy, const uint32_t msg[8], const uint32
             fe9_cmov(P.y, ny, ((c >> (GLV_W - 1)) != 0) != ng);
             if (i == GLV_DIGITS - 1 && j == 0) {  // the top digit starts the sum (Z = 1), no add
                 acc.x = P.x;
-                acc.y = P.y;
+                fe9_add(acc.y, P.y, P.y);  // W = 2y, 4
                 fe9_normalize_weak(acc.y);
                 fe9_set_u32(acc.z, 1);
                 ainf = false;
                 continue;
             }
-            gej9_add_ge(acc, ainf, acc, P);
+            gejw_add_ge(acc, ainf, acc, P);
         }
     }
+    gejw_to_gej9(acc, acc);  // (X, W, Z) -> Jacobian, Z magnitude 2
     fe9_mul(acc.z, acc.z, zfac);  // back from E'' to E_t (2*1 -> 1)
 
     // ---- u1 * G via comb

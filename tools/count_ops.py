@@ -15,7 +15,8 @@ tools/build_variant.sh opcount -DGSV_OPCOUNT`), at the bench's batch sizes:
 roofline) our kernels execute, from the op counts and each op's mad count in our limb layout:
 a secp256k1 fe9 product 81 + 27 (column form 3 of tools/gen_fe9_asm.py: 7 high-column carries, 17
 2^261 folds, 3 in the 2^256 fold; a product with an addend has 9 more, counted as a product), a
-squaring 45 + 27, a dot product 162 + 27,
+squaring 45 + 27 (fe9_sqr3 is counted as a squaring), a dot product 162 + 27, a product plus a
+square with one reduction (fe9_dot_ms, the W doubling's) 81 + 45 + 27,
 a scalar product 64 (8 x 32-bit limbs; the folds mod n are not counted, < 1 %), a BN254 F_p product
 81 (9 x 29-bit) and a BN254 Montgomery reduction 81 (one per fq_mul / fq_mul2 / fq_dot, shared by
 the products it sums).  Safegcd inversions are counted separately (their divsteps are not mads).
@@ -38,11 +39,11 @@ import torch  # noqa: E402
 import gsv  # noqa: E402
 from gsv import _lib  # noqa: E402
 
-KINDS = ["fe_mul", "fe_sqr", "sc_mul", "sc_sqr", "bn_mul", "modinv", "bn_redc", "fe_dot"]
+KINDS = ["fe_mul", "fe_sqr", "sc_mul", "sc_sqr", "bn_mul", "modinv", "bn_redc", "fe_dot", "fe_dot_ms"]
 
 
 def read(tu):
-    buf = (ctypes.c_ulonglong * 8)()
+    buf = (ctypes.c_ulonglong * len(KINDS))()
     rc = getattr(_lib.load(), f"gsv_opcount_{tu}")(buf, 1)
     assert rc == 0, f"gsv_opcount_{tu} failed (is {os.environ['GSV_LIB_PATH']} the -DGSV_OPCOUNT build?)"
     return dict(zip(KINDS, list(buf)[:len(KINDS)]))
@@ -55,7 +56,7 @@ def per_unit(c, n):
 def main():
     ctx = gsv.Context(0)
     dev = torch.device("cuda", 0)
-    W = {"fe_mul": 108, "fe_sqr": 72, "sc_mul": 64, "sc_sqr": 36, "bn_mul": 81, "bn_redc": 81, "fe_dot": 189}
+    W = {"fe_mul": 108, "fe_sqr": 72, "sc_mul": 64, "sc_sqr": 36, "bn_mul": 81, "bn_redc": 81, "fe_dot": 189, "fe_dot_ms": 153}
     out = {"build": "variants/opcount (-DGSV_OPCOUNT)", "unit": "v_mad_u64_u32 per unit of work",
            "weights_mad_per_op": W}
     # ---- configs[1]: 2^20 recoveries
@@ -72,7 +73,7 @@ def main():
     torch.cuda.synchronize()
     assert int(st.max()) == 0
     c = per_unit(read("ecrecover"), n)
-    c["mac_equiv"] = round(sum(W[k] * c.get(k, 0) for k in ("fe_mul", "fe_sqr", "sc_mul", "sc_sqr", "fe_dot")), 1)
+    c["mac_equiv"] = round(sum(W[k] * c.get(k, 0) for k in ("fe_mul", "fe_sqr", "sc_mul", "sc_sqr", "fe_dot", "fe_dot_ms")), 1)
     out["recovery"] = c
     # ---- configs[4]: 4-pair checks, one GPU's batch and the 8-rank per-rank batch
     for name, nchk in (("pairing_check", 65536), ("pairing_check_8192", 8192)):
@@ -108,7 +109,7 @@ def main():
     torch.cuda.synchronize()
     assert torch.equal(stt.view(-1), exp)
     c = per_unit(read("notary"), nsh * txs)
-    c["mac_equiv"] = round(sum(W[k] * c.get(k, 0) for k in ("fe_mul", "fe_sqr", "sc_mul", "sc_sqr", "fe_dot")), 1)
+    c["mac_equiv"] = round(sum(W[k] * c.get(k, 0) for k in ("fe_mul", "fe_sqr", "sc_mul", "sc_sqr", "fe_dot", "fe_dot_ms")), 1)
     out["notary_tx"] = c
     # ---- the G1 precompiles: both multiplication forms and the addition
     n = 65536

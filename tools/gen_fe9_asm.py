@@ -56,6 +56,27 @@ def SQR_TERMS(k):
     return t
 
 
+def DOT_MS_TERMS(k):
+    """a b + c^2 with d = 2c limb-wise (fe9_dot_ms: the W doubling's -W3 = E 2(X3 - D) + B B): the
+    product's 81 terms, the squaring's cross terms c[i] * d[j] (i < j) and its diagonal c[k/2]^2 in one
+    column chain, one reduction.  Bound m_a m_b + m_c^2 <= 7: a column's terms sum to < 63 2^58, as
+    for fe9_mul."""
+    t = MUL_TERMS(k) + [(18 + i, 27 + (k - i)) for i in range(9) if i < k - i < 9]
+    if k % 2 == 0 and k // 2 < 9:
+        t.append((18 + k // 2, 18 + k // 2))
+    return t
+
+
+def SQR3_TERMS(k):
+    """3 a^2 with b = 6a and c = 3a limb-wise (fe9_sqr3: the doubling's E = 3 X^2): cross terms
+    a[i] * 6a[j] (i < j) + a[k/2] * 3a[k/2].  Bound m_a <= 1.33 (6a fits 32 bits; 3 m_a^2 <= 5.4): the
+    multiply-by-3 of a reduced square and its normalisation become part of the squaring."""
+    t = [(i, 9 + (k - i)) for i in range(9) if i < k - i < 9]
+    if k % 2 == 0 and k // 2 < 9:
+        t.append((k // 2, 18 + k // 2))
+    return t
+
+
 def full_lines(terms_of_column, addend=False):
     """Product + reduction (secp256k1_fe9.cuh fe9_reduce restated) in one statement.  Operands:
     %0..%8 r (o_0..o_8 in place), %9..%16 o_9..o_16, %17 sd, %18..%26 a, %27..%35 b,
@@ -305,18 +326,19 @@ def full_lines3(terms_of_column, addend=False):
     return L
 
 
-def full2(name, doc, terms_of_column, addend=False, dot=False, gen=None):
+def full2(name, doc, terms_of_column, addend=False, dot=False, gen=None, third=False):
+    """third: a third operand array c that the terms read (no addend, no d)"""
     L = (gen or full_lines2)(terms_of_column, addend)
     outs = ", ".join([f'"=&v"(r[{i}])' for i in range(9)] + ['"=&s"(sd)'])
     ins = ", ".join([f'"v"(a[{i}])' for i in range(9)] + [f'"v"(b[{j}])' for j in range(9)] +
                     ['"s"(k31264)', '"s"(k256)', '"s"(k977)', '"s"(k8192)'] +
-                    ([f'"v"(c[{j}])' for j in range(9)] if addend or dot else []) +
+                    ([f'"v"(c[{j}])' for j in range(9)] if addend or dot or third else []) +
                     ([f'"v"(d[{j}])' for j in range(9)] if dot else []))
     body = "\\n\\t".join(L)
     clob = ", ".join(f'"v{i}"' for i in range(2, 20))
     return [f"// {doc}",
             f"__device__ __forceinline__ void {name}(uint32_t r[9], const uint32_t a[9], const uint32_t b[9]"
-            + (", const uint32_t c[9]" if addend or dot else "") + (", const uint32_t d[9]" if dot else "") + ") {",
+            + (", const uint32_t c[9]" if addend or dot or third else "") + (", const uint32_t d[9]" if dot else "") + ") {",
             "    uint64_t sd;",
             "    uint32_t k31264 = 31264u, k256 = 256u, k977 = 977u, k8192 = 8192u;",
             f'    asm("{body}"',
@@ -339,9 +361,13 @@ def main():
              ("fe9_mul_add_full", "r = a * b + c mod p, c limbs < 2^31 (fe9_mul_add's contract)", MUL_TERMS, True, False),
              ("fe9_sqr_add_full", "r = a^2 + c mod p with b = 2a limb-wise, c limbs < 2^31 (fe9_sqr_add's contract)",
               SQR_TERMS, True, False),
-             ("fe9_dot_full", "r = a * b + c * d mod p, one reduction (fe9_dot's contract)", DOT_TERMS, False, True)]
+             ("fe9_dot_full", "r = a * b + c * d mod p, one reduction (fe9_dot's contract)", DOT_TERMS, False, True),
+             ("fe9_dot_ms_full", "r = a * b + c^2 mod p with d = 2c limb-wise, one reduction (fe9_dot_ms's contract)",
+              DOT_MS_TERMS, False, True),
+             ("fe9_sqr3_full", "r = 3 a^2 mod p with b = 6a, c = 3a limb-wise (fe9_sqr3's contract)",
+              SQR3_TERMS, False, "third")]
     for name, doc, terms, add, dot in specs:
-        out += full2(name, doc, terms, add, dot, gen=full_lines3)
+        out += full2(name, doc, terms, add, dot is True, gen=full_lines3, third=dot == "third")
     out.append("}  // namespace gsv")
     with open(OUT, "w") as f:
         f.write("\n".join(out) + "\n")
