@@ -12,7 +12,7 @@
 //
 // Pipeline per batch: k_header_hash (one lane per header: each RLP preimage assembled in LDS, two
 // Keccak-256s) -> k_ecrecover (the shared recovery kernel, address output) -> k_header_compare
-// (signer vs ProposerAddress).
+// (signer vs ProposerAddress; a header whose signature is nil gets GSV_ST_INVALID_SIG_LEN there).
 #include <hip/hip_runtime.h>
 
 #include "opcount.cuh"
@@ -148,14 +148,19 @@ __global__ __launch_bounds__(256) void k_header_compare(const uint8_t* __restric
                                                         uint8_t* status, uint8_t* signer20) {
     uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    uint8_t st = status[i];
+    uint8_t nf = nil_flags ? nil_flags[i] : 0;
+    // a nil/empty ProposerSignature: crypto.Ecrecover returns ErrInvalidSignatureLen
+    // (crypto/secp256k1/secp256.go:171-174) whatever the sig65 row held when k_ecrecover read it
+    uint8_t st = (nf & 4) ? GSV_ST_INVALID_SIG_LEN : status[i];
     const uint8_t* r = rec20 + (size_t)i * 20;
     const uint8_t* p = prop20 + (size_t)i * 20;
-    bool eq = st == GSV_ST_OK && !(nil_flags && (nil_flags[i] & 2));
+    bool rec = st == GSV_ST_OK;
+    bool eq = rec && !(nf & 2);
     for (int k = 0; k < 20; k++) eq = eq && r[k] == p[k];
-    if (st == GSV_ST_OK && !eq) status[i] = GSV_ST_PROPOSER_MISMATCH;
+    if (nf & 4) status[i] = st;
+    else if (rec && !eq) status[i] = GSV_ST_PROPOSER_MISMATCH;
     if (signer20)
-        for (int k = 0; k < 20; k++) signer20[(size_t)i * 20 + k] = st == GSV_ST_OK ? r[k] : 0;
+        for (int k = 0; k < 20; k++) signer20[(size_t)i * 20 + k] = rec ? r[k] : 0;
 }
 
 size_t header_scratch_bytes(uint32_t n) { return (size_t)n * (32 + 20); }

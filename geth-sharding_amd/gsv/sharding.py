@@ -111,7 +111,8 @@ def HeaderHashBatch(headers, ctx=None) -> np.ndarray:
 def VerifyProposerSignatures(headers, ctx=None):
     """-> (signers (n,20), status (n,)): GSV_ST_OK when the signature over the unsigned header hash
     recovers ProposerAddress, GSV_ST_PROPOSER_MISMATCH when it recovers another address, else the
-    recovery status (crypto.Ecrecover errors)."""
+    recovery status (crypto.Ecrecover errors).  A header without a signature (Sig() None or empty) is
+    never recovered: GSV_ST_INVALID_SIG_LEN (secp256k1.ErrInvalidSignatureLen) and a zero signer."""
     _, signer, st = (ctx or default_context()).collation_header_verify_batch(*_pack_headers(headers))
     return signer, st
 

@@ -341,7 +341,10 @@ int gsv_collation_poc_batch_dev(gsv_ctx *ctx, const uint8_t *d_bodies, const uin
  * signer20_out (optional): crypto.Ecrecover(Hash() with ProposerSignature empty — the hash the
  * proposer signs at sharding/proposer/proposer.go:83 — , sig) -> address, zero on failure.
  * status: GSV_ST_OK when the signer equals ProposerAddress, GSV_ST_PROPOSER_MISMATCH when not,
- * else the recovery status (GSV_ST_INVALID_RECID / GSV_ST_RECOVER_FAILED). */
+ * else the recovery status (GSV_ST_INVALID_RECID / GSV_ST_RECOVER_FAILED).  A header with nil bit 2
+ * set is never recovered: crypto.Ecrecover on an empty signature returns ErrInvalidSignatureLen
+ * (crypto/secp256k1/secp256.go:171-174), so its status is GSV_ST_INVALID_SIG_LEN and its signer zero
+ * whatever its sig65 row holds; its hash32_out is the hash with the signature empty. */
 int gsv_collation_header_verify_batch(gsv_ctx *ctx, const uint8_t *shard_id32, const uint8_t *chunk_root32,
                                       const uint8_t *period32, const uint8_t *proposer20, const uint8_t *sig65,
                                       const uint8_t *nil_flags, size_t n, uint8_t *hash32_out,

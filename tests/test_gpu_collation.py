@@ -42,6 +42,21 @@ def test_derive_sha_random_vs_oracle(ctx, oracle):
         assert bytes(out[i]) == oracle.derive_sha(lst), (i, len(lst))
 
 
+def test_derive_sha_hashed_leaves_past_65536_items(ctx, oracle):
+    """Item j's key is rlp(uint(j)): three bytes of integer from j = 65,536.  k_derive_leaf builds a
+    hashed leaf's header (values of >= 32 bytes; shorter ones are inlined in their parent) in registers
+    around that key, so the lists carry values of 32, 33, 60 and 140 bytes past that index, next to
+    inlined ones.  Two lists of one length share one plan."""
+    rng = random.Random(65536)
+    lists = [[rng.randbytes(rng.choice([0, 1, 31, 32, 33, 60, 140])) for _ in range(65836)] for _ in range(2)]
+    for lst in lists:
+        assert {len(v) for v in lst[65536:]} == {0, 1, 31, 32, 33, 60, 140}
+        assert sum(len(v) >= 32 for v in lst[65536:]) > 100
+    out = ctx.derive_sha_batch(lists)
+    for i, lst in enumerate(lists):
+        assert bytes(out[i]) == oracle.derive_sha(lst), i
+
+
 def test_derive_sha_byte_lists_equal_chunk_root(ctx):
     # Chunks(body).GetRlp(j) as explicit items == the specialised chunk-root kernels
     rng = np.random.default_rng(3)
@@ -85,15 +100,16 @@ def test_poc_batch_vs_oracle(ctx, oracle):
         assert bytes(out[i]) == oracle.calculate_poc(b, salt), i
 
 
-@pytest.mark.parametrize("slen", [0, 1, 3, 15, 16, 17, 20, 33, 255, 9000])
+@pytest.mark.parametrize("slen", [0, 1, 3, 15, 16, 17, 20, 33, 255, 8191, 8192, 8193, 9000])
 def test_poc_salt_lengths_vs_oracle(ctx, oracle, slen):
     """k_poc_expand writes 16 salted bytes per thread from the period-(s+1) pattern staged in LDS plus
     the window's body bytes (one or more per window below s = 15, at most one from s = 15 up; every
-    window phase); salts past its LDS bound (8,192 bytes) take k_poc_expand_bytes.  Bodies of 0-1,037
-    bytes, so salted lengths end at every phase of a 16-byte store."""
+    window phase); salts past its LDS bound (8,192 bytes) take k_poc_expand_bytes: 8,191 and 8,192 are
+    the last two salts of the first kernel, 8,193 the first of the second.  Bodies of 0-1,037 bytes
+    (0-100 under the long salts), so salted lengths end at every phase of a 16-byte store."""
     rng = np.random.default_rng(100 + slen)
     salt = rng.integers(0, 256, slen, dtype=np.uint8).tobytes()
-    lens = [0, 1, 2, 15, 16, 17, 100, 1037] if slen < 9000 else [0, 1, 7, 100]
+    lens = [0, 1, 2, 15, 16, 17, 100, 1037] if slen < 8191 else [0, 1, 7, 100]
     bodies = [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in lens]
     out = ctx.collation_poc_batch(bodies, salt)
     for i, b in enumerate(bodies):
