@@ -246,7 +246,7 @@ GSV_DI void keccak256_xy(uint32_t h[8], const uint32_t x[8], const uint32_t y[8]
     }
     a[8] = 0x01;
     a[16] = 0x8000000000000000ULL;
-    keccakf(a);
+    keccakf_digest(a);  // the one permutation: only the digest's words 0..3 are read
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         h[2 * j] = (uint32_t)a[j];

@@ -15,6 +15,7 @@ __device__ void gejw_dbl_rare(gej9& o, const gej9& p);
 #define GEJW_DBL_RARE(o, p) gejw_dbl_rare(o, p)
 #include "secp256k1_fe9.cuh"
 #include "modinv30.cuh"
+#include "glv_sched.cuh"
 
 namespace gsv {
 
@@ -24,6 +25,8 @@ __device__ constexpr uint32_t MINUS_LAMBDA[8] = {0xB51283CFu, 0xE0CFC810u, 0x8EC
                                                  0x77ED9BA4u, 0x5AD9E3FDu, 0x3FA3CF1Fu, 0xAC9C52B3u};
 __device__ constexpr uint32_t MINUS_B1[8] = {0x0ABFE4C3u, 0x6F547FA9u, 0x010E8828u, 0xE4437ED6u,
                                              0u, 0u, 0u, 0u};
+// -b2 mod n: what libsecp256k1's split multiplies by (tests/secp_glv_model.py reads it); the device
+// multiplies by b2 = n - MINUS_B2 (GLV_B2 at sc_split_lambda) and subtracts
 __device__ constexpr uint32_t MINUS_B2[8] = {0x3DB1562Cu, 0xD765CDA8u, 0x0774346Du, 0x8A280AC5u,
                                              0xFFFFFFFEu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
 __device__ constexpr uint32_t GLV_G1[8] = {0xEB153DABu, 0x90E49284u, 0x6BCDE86Cu, 0xD221A7D4u,
@@ -94,16 +97,26 @@ GSV_DI void sc_mul_shift272(sc& r, const sc& k, const uint32_t g[8]) {
     }
 }
 
-// k = r1 + r2 * lambda (mod n)  (libsecp256k1 scalar_impl.h secp256k1_scalar_split_lambda)
+// k = r1 + r2 * lambda (mod n)  (libsecp256k1 scalar_impl.h secp256k1_scalar_split_lambda):
+// r2 = c1 (-b1) + c2 (-b2), r1 = k - r2 lambda, with c_i = round(k g_i / 2^272).
+// The two products of r2 are short.  k < 2^256, so c_i <= (2^256 g_i) / 2^272 + 1 = g_i / 2^16 + 1:
+// g1 < 2^142 gives c1 < 2^126, g2 < 2^144 with g2 >> 16 = 0xE4437ED6...E4C4 gives c2 < 2^128.
+// -b1 = MINUS_B1 < 2^128 and b2 = n - MINUS_B2 = GLV_B2 < 2^126 (it is the lattice's a1, GLV_V1A).
+// So c1 (-b1) < 2^254 and c2 b2 < 2^254 are 4 x 4-limb products, both below n: no reduction, and
+// r2 = c1 (-b1) - c2 b2 + (n if that is negative) is the same residue sc_mul and sc_add gave
+// (c2 (-b2) = c2 n - c2 b2).  tests/test_secp_recover_trim.py asserts the four bounds on the model's
+// boundary scalars.  (Not counted as OPC_SC_MUL: tools/count_ops.py reads two scalar products fewer.)
+__device__ constexpr uint32_t GLV_B2[4] = {0x9284EB15u, 0xE86C90E4u, 0xA7D46BCDu, 0x3086D221u};
 GSV_DI void sc_split_lambda(sc& r1, sc& r2, const sc& k) {
     sc c1, c2, t;
     sc_mul_shift272(c1, k, GLV_G1);
     sc_mul_shift272(c2, k, GLV_G2);
-    sc_from_const(t, MINUS_B1);
-    sc_mul(c1, c1, t);
-    sc_from_const(t, MINUS_B2);
-    sc_mul(c2, c2, t);
-    sc_add(r2, c1, c2);
+    const uint32_t nb1[4] = {MINUS_B1[0], MINUS_B1[1], MINUS_B1[2], MINUS_B1[3]};
+    const uint32_t b2[4] = {GLV_B2[0], GLV_B2[1], GLV_B2[2], GLV_B2[3]};
+    uint32_t n[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) n[i] = SN[i];
+    glv_short_r2(r2.v, c1.v, nb1, c2.v, b2, n);
     sc_from_const(t, MINUS_LAMBDA);
     sc_mul(r1, r2, t);
     sc_add(r1, r1, k);
@@ -111,49 +124,9 @@ GSV_DI void sc_split_lambda(sc& r1, sc& r2, const sc& k) {
 
 GSV_DI bool sc_is_high(const sc& a) { return limbs_lt(HALF_N, a.v); }
 
-// Fixed-schedule odd-digit recoding, w = GLV_W: k (odd after skew) = sum d_i 2^(w i) with
-// d_i odd in [-(2^w - 1), 2^w - 1].  Digit i packed in a DIG_SLOT-bit slot: bit w - 1 = negative,
-// bits 0 .. w - 2 = (|d| - 1) / 2.
-GSV_DI void recode_glv(uint32_t dig[DIG_WORDS], uint32_t& skew, const sc& kin) {
-    constexpr uint32_t MASK = (2u << GLV_W) - 1u;
-    constexpr int32_t OFF = 1 << GLV_W;
-    uint32_t k[5] = {kin.v[0], kin.v[1], kin.v[2], kin.v[3], kin.v[4]};
-    skew = (k[0] & 1u) ^ 1u;
-    // k += skew  (k < 2^129 so no overflow out of 5 limbs)
-    uint64_t c = (uint64_t)k[0] + skew;
-    k[0] = lo32(c);
-#pragma unroll
-    for (int i = 1; i < 5; i++) {
-        c = (uint64_t)k[i] + hi32(c);
-        k[i] = lo32(c);
-    }
-#pragma unroll
-    for (int i = 0; i < DIG_WORDS; i++) dig[i] = 0;
-#pragma unroll
-    for (int i = 0; i < GLV_DIGITS; i++) {
-        int32_t d;
-        if (i < GLV_DIGITS - 1) d = (int32_t)(k[0] & MASK) - OFF;
-        else d = (int32_t)(k[0] & MASK);
-        uint32_t neg = d < 0 ? 1u : 0u;
-        uint32_t mag = (uint32_t)(d < 0 ? -d : d);
-        uint32_t code = (neg << (GLV_W - 1)) | ((mag - 1u) >> 1);
-        dig[i / DIG_PER_WORD] |= code << ((i % DIG_PER_WORD) * DIG_SLOT);
-        // k = (k - d) >> w
-        int64_t t = (int64_t)k[0] - d;
-        uint32_t kk[5];
-        kk[0] = (uint32_t)t;
-        int64_t carry = t >> 32;
-#pragma unroll
-        for (int j = 1; j < 5; j++) {
-            int64_t u = (int64_t)k[j] + carry;
-            kk[j] = (uint32_t)u;
-            carry = u >> 32;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++) k[j] = (kk[j] >> GLV_W) | (kk[j + 1] << (32 - GLV_W));
-        k[4] = kk[4] >> GLV_W;
-    }
-}
+// The ladder's digits are read from the scalar's bits where they are used (glv_sched.cuh says why
+// that is the fixed-schedule odd-digit recoding): K = k >> 1 in DIG_WORDS words, digit i in slot i.
+static_assert(DIG_SLOT == GLV_W, "the digits are read in place: slot i of the halved scalar is K_i");
 
 // ---------------------------------------------------------------------------- group helpers
 // Field elements are fe9 (secp256k1_fe9.cuh); the magnitude of every intermediate is noted.
@@ -265,9 +238,33 @@ GSV_DI void comb_mul_g9(gej9& acc, bool& inf, const sc& u, const uint4* __restri
     fe9_set_u32(acc.z, 1);
     inf = d0 == 0;
     comb_shift(c);  // c = u >> (COMB_BITS w) at the top of window w
-    gtab_load(Pn, gtab + (((size_t)1 << COMB_BITS) + (c[0] & MASK)) * GTAB_ENTRY_U4);
+    const uint32_t d1 = c[0] & MASK;
+    gtab_load(Pn, gtab + (((size_t)1 << COMB_BITS) + d1) * GTAB_ENTRY_U4);
+    // No add of the comb doubles or cancels (before window w the sum is
+    // (u mod 2^(COMB_BITS w)) G, below the addend d 2^(COMB_BITS w) G, and the two together stay at or
+    // below u < n), so none tests H: gejw_add_ge_z1 / gejw_add_ge_nx.  What does occur is the identity
+    // start: low windows of u that are zero carry inf, and the addend becomes the accumulator.
+    // Window 1 adds to window 0's entry, still affine (Z = 1).
+    {
+        ge9 P = Pn;
+        if (COMB_WINDOWS > 2) {
+            comb_shift(c);
+            gtab_load(Pn, gtab + (((size_t)2 << COMB_BITS) + (c[0] & MASK)) * GTAB_ENTRY_U4);
+        }
+        gej9 t;
+        gejw_add_ge_z1(t, acc, P);
+        if (FE9_ANY(inf)) {
+            gej9 qn;
+            gejw_from_ge(qn, P);
+            gej9_cmov(t, qn, inf);
+        }
+        if (d1 != 0) {
+            acc = t;
+            inf = false;
+        }
+    }
 #pragma unroll 1
-    for (int w = 1; w < COMB_WINDOWS; w++) {
+    for (int w = 2; w < COMB_WINDOWS; w++) {
         uint32_t d = c[0] & MASK;
         ge9 P = Pn;
         if (w < COMB_WINDOWS - 1) {  // prefetch next window's entry
@@ -276,7 +273,7 @@ GSV_DI void comb_mul_g9(gej9& acc, bool& inf, const sc& u, const uint4* __restri
         }
         gej9 t;
         bool tinf = inf;
-        gejw_add_ge(t, tinf, acc, P);
+        gejw_add_ge_nx(t, tinf, acc, P);
         if (d != 0) {
             acc = t;
             inf = tinf;
@@ -521,9 +518,9 @@ GSV_DI uint32_t recover_core(fe& qx, fe& qy, const uint32_t msg[8], const uint32
 #pragma unroll
         for (int i = 0; i < 8; i++) k2.v[i] = neg2 ? nk.v[i] : k2.v[i];
     }
-    uint32_t dig1[DIG_WORDS], dig2[DIG_WORDS], skew1, skew2;  // skews 0 (odd halves)
-    recode_glv(dig1, skew1, k1);
-    recode_glv(dig2, skew2, k2);
+    uint32_t K1[DIG_WORDS], K2[DIG_WORDS];  // the halved magnitudes: digit i sits in slot i
+    glv_halve(K1, k1.v);
+    glv_halve(K2, k2.v);
 
     // The GLV table {x[GLV_NT], y[GLV_NT]} of the odd multiples (2e+1)R lives in LDS (w = 3:
     // ltab = this lane's column of a [word][256 lanes] array, conflict-free for any per-lane entry
@@ -587,64 +584,74 @@ GSV_DI uint32_t recover_core(fe& qx, fe& qy, const uint32_t msg[8], const uint32
         fe9_mul(zfac, f, zd);  // f = all the z-ratios: the entries' common Z on E is zd f
     }
 
+    // One entry of the table for the add of pass j (0: T, 1: lambda(T) = (beta x, y)), negated where
+    // the digit's sign and the half's sign differ: x, y magnitude <= 1, <= 2.  (A macro, not a lambda: a
+    // captured ptab turns both halves of the table into flat loads through 64-bit addresses.)
+#define GLV_ENTRY(P, ei, negate, j)                                                                    \
+    do {                                                                                               \
+        if (GLV_LNT == GLV_NT || (GLV_LNT > 0 && (ei) < (uint32_t)GLV_LNT)) {                          \
+            uint32_t xo = (ei) * 9u;                                                                   \
+            _Pragma("unroll") for (int k = 0; k < 9; k++) {                                            \
+                P.x.v[k] = GLV_L(xo + k);                                                              \
+                P.y.v[k] = GLV_L(9u * GLV_LNT + xo + k);                                               \
+            }                                                                                          \
+        } else { /* the lanes whose digit indexes the private part (divergent: each side loads only its lanes) */ \
+            uint32_t xo = ((ei) - (uint32_t)GLV_LNT) * 9u;                                             \
+            _Pragma("unroll") for (int k = 0; k < 9; k++) {                                            \
+                P.x.v[k] = ptab[xo + k];                                                               \
+                P.y.v[k] = ptab[9u * PNT + xo + k];                                                    \
+            }                                                                                          \
+        }                                                                                              \
+        if ((j) != 0) { /* wave-uniform */                                                             \
+            fe9 beta;                                                                                  \
+            fe9_from_const(beta, BETA);                                                                \
+            fe9_mul(P.x, P.x, beta);                                                                   \
+        }                                                                                              \
+        fe9 ny;                                                                                        \
+        fe9_neg<1>(ny, P.y); /* 2 */                                                                   \
+        fe9_cmov(P.y, ny, (negate));                                                                   \
+    } while (0)
     gej9 acc;  // W convention (X, 2Y, Z) through the ladder
-    bool ainf = true;
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-        acc.x.v[k] = GLV_X(0, k);
-        acc.y.v[k] = GLV_Y(0, k);
+    // The top digits (positive, index K >> w (GLV_DIGITS - 1)): the k1 entry starts the sum (Z = 1) and
+    // the k2 entry is added to it as affine + affine (gejw_add_ge_z1).  That add meets no exceptional
+    // case: its operands are +-(2a + 1) R and +-(2b + 1) lambda R with a, b < GLV_NT, equal or opposite
+    // only if (2a + 1) == +-lambda (2b + 1) (mod n), R having order n, and no such pair exists
+    // (tests/test_secp_recover_trim.py tries all of them).  u2 R = O cannot come out of it either.
+    static_assert((GLV_DIGITS - 1) % DIG_PER_WORD == 0, "the top digit is the low slot of the last word");
+    {
+        ge9 P;
+        uint32_t e1 = glv_slot<DIG_SLOT>(K1[DIG_WORDS - 1], GLV_DIGITS - 1) & (uint32_t)(GLV_NT - 1);
+        uint32_t e2 = glv_slot<DIG_SLOT>(K2[DIG_WORDS - 1], GLV_DIGITS - 1) & (uint32_t)(GLV_NT - 1);
+        GLV_ENTRY(P, e1, neg1, 0);
+        acc.x = P.x;                     // 1 (an entry's x is a product's output)
+        fe9_add(acc.y, P.y, P.y);        // W = 2y, 4
+        fe9_normalize_weak(acc.y);       // 1
+        GLV_ENTRY(P, e2, neg2, 1);
+        gej9 t;
+        gejw_add_ge_z1(t, acc, P);
+        acc = t;
     }
-    fe9_set_u32(acc.z, 1);
+    bool ainf = false;
 #pragma unroll 1
-    for (int i = GLV_DIGITS - 1; i >= 0; i--) {
-        if (i != GLV_DIGITS - 1) {
+    for (int i = GLV_DIGITS - 2; i >= 0; i--) {
 #pragma unroll 1
-            for (int d = 0; d < GLV_W; d++) gejw_dbl_neg(acc, acc);  // -2P each: + again after GLV_W
-        }
-        constexpr uint32_t CMASK = (1u << DIG_SLOT) - 1u;
-        uint32_t c1 = (sel_word(dig1, (uint32_t)i / DIG_PER_WORD) >> ((i % DIG_PER_WORD) * DIG_SLOT)) & CMASK;
-        uint32_t c2 = (sel_word(dig2, (uint32_t)i / DIG_PER_WORD) >> ((i % DIG_PER_WORD) * DIG_SLOT)) & CMASK;
+        for (int d = 0; d < GLV_W; d++) gejw_dbl_neg(acc, acc);  // -2P each: + again after GLV_W
         // one add body, two passes: digit of k1 on T, digit of k2 on lambda(T) = (beta x, y)
 #pragma unroll 1
         for (int j = 0; j < 2; j++) {
-            uint32_t c = j ? c2 : c1;
-            bool ng = j ? neg2 : neg1;
-            uint32_t ei = c & (uint32_t)(GLV_NT - 1);
+            uint32_t ei;
+            bool dneg;
+            glv_digit<GLV_W>(ei, dneg, glv_slot<DIG_SLOT>(j ? K2[DIG_WORDS - 2] : K1[DIG_WORDS - 2], i));
             ge9 P;
-            if (GLV_LNT == GLV_NT || (GLV_LNT > 0 && ei < (uint32_t)GLV_LNT)) {
-                uint32_t xo = ei * 9u;
-#pragma unroll
-                for (int k = 0; k < 9; k++) {
-                    P.x.v[k] = GLV_L(xo + k);
-                    P.y.v[k] = GLV_L(9u * GLV_LNT + xo + k);
-                }
-            } else {  // the lanes whose digit indexes the private part (divergent: each side loads only its lanes)
-                uint32_t xo = (ei - (uint32_t)GLV_LNT) * 9u;
-#pragma unroll
-                for (int k = 0; k < 9; k++) {
-                    P.x.v[k] = ptab[xo + k];
-                    P.y.v[k] = ptab[9u * PNT + xo + k];
-                }
-            }
-            if (j != 0) {  // wave-uniform
-                fe9 beta;
-                fe9_from_const(beta, BETA);
-                fe9_mul(P.x, P.x, beta);
-            }
-            fe9 ny;
-            fe9_neg<1>(ny, P.y);         // 2
-            fe9_cmov(P.y, ny, ((c >> (GLV_W - 1)) != 0) != ng);
-            if (i == GLV_DIGITS - 1 && j == 0) {  // the top digit starts the sum (Z = 1), no add
-                acc.x = P.x;
-                fe9_add(acc.y, P.y, P.y);  // W = 2y, 4
-                fe9_normalize_weak(acc.y);
-                fe9_set_u32(acc.z, 1);
-                ainf = false;
-                continue;
-            }
+            GLV_ENTRY(P, ei, dneg != (j ? neg2 : neg1), j);
             gejw_add_ge(acc, ainf, acc, P);
         }
+        if (i % DIG_PER_WORD == 0) {  // wave-uniform: the word is used up
+            glv_next_word(K1);
+            glv_next_word(K2);
+        }
     }
+#undef GLV_ENTRY
     gejw_to_gej9(acc, acc);  // (X, W, Z) -> Jacobian, Z magnitude 2
     fe9_mul(acc.z, acc.z, zfac);  // back from E'' to E_t (2*1 -> 1)
 
@@ -675,7 +682,7 @@ GSV_DI void store_pub_addr(uint8_t* pub65, uint8_t* addr20, bool ok, const fe& q
     }
     if (addr20) {
         uint32_t h[8];
-        keccak256_xy(h, qx.v, qy.v);
+        keccak256_xy(h, qx.v, qy.v);  // one permutation, in digest form
         // hash bytes 12..31 = words 3..7 (little-endian byte order within words)
 #pragma unroll
         for (int w = 3; w < 8; w++)
