@@ -1,8 +1,10 @@
-// Stateless batches of the C ABI (gsv_ctx.h): Keccak-256, ecrecover and its precompile, bn256Add /
-// bn256ScalarMul, recoverPlain over decoded fields, the synthetic signer, types.Sender over tx RLP.
+// Stateless batches of the C ABI (gsv_ctx.h): Keccak-256, ecrecover and its precompile, ECDSA
+// verification and public-key parsing, bn256Add / bn256ScalarMul, recoverPlain over decoded fields,
+// the synthetic signer, types.Sender over tx RLP.
 #include <thread>
 
 #include "gsv_ctx.h"
+#include "pubkey_pack.h"
 #include "tx_host.h"
 
 using namespace gsv::api;
@@ -78,6 +80,82 @@ int gsv_ecrecover_batch(gsv_ctx* c, const uint8_t* msg32, const uint8_t* sig65, 
     if (pub65_out) HIPCHK(hipMemcpyAsync(pub65_out, d_pub, n * 65, hipMemcpyDeviceToHost, c->stream));
     if (addr20_out) HIPCHK(hipMemcpyAsync(addr20_out, d_addr, n * 20, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return GSV_SUCCESS;
+}
+
+// ------------------------------------------------------------------ ECDSA verification, public-key parsing
+int gsv_ecdsa_verify_batch_dev(gsv_ctx* c, const uint8_t* d_msg32, const uint8_t* d_sig64, const uint8_t* d_pub65,
+                               const uint8_t* d_publen, size_t n, uint8_t* d_ok, void* stream) {
+    if (!c || (n && (!d_msg32 || !d_sig64 || !d_pub65 || !d_publen || !d_ok)) || n > 0xFFFFFFFFull)
+        return GSV_E_INVALID_ARG;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    KTimer t(c, GSV_K_ECRECOVER, st);
+    return hip_err(gsv::launch_ecverify(d_msg32, d_sig64, d_pub65, d_publen, (uint32_t)n, c->gtab, d_ok, st));
+}
+
+int gsv_pubkey_parse_batch_dev(gsv_ctx* c, const uint8_t* d_pub65, const uint8_t* d_publen, size_t n,
+                               uint8_t* d_pub65_out, uint8_t* d_ok, void* stream) {
+    if (!c || (n && (!d_pub65 || !d_publen || !d_pub65_out || !d_ok)) || n > 0xFFFFFFFFull)
+        return GSV_E_INVALID_ARG;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    KTimer t(c, GSV_K_ECRECOVER, st);
+    return hip_err(gsv::launch_pubkey_parse(d_pub65, d_publen, (uint32_t)n, d_pub65_out, d_ok, st));
+}
+
+// the offset table of a host form: ascending, and a buffer behind any key that has bytes
+static bool key_offsets_ok(const uint8_t* pub, const uint64_t* off, size_t n) {
+    for (size_t i = 0; i < n; i++)
+        if (off[i + 1] < off[i]) return false;
+    return off[n] == off[0] || pub;
+}
+
+int gsv_ecdsa_verify_batch(gsv_ctx* c, const uint8_t* msg32, const uint8_t* sig64, const uint8_t* pub,
+                           const uint64_t* pub_off, size_t n, uint8_t* ok) {
+    if (!c || (n && (!msg32 || !sig64 || !pub_off || !ok)) || n > 0xFFFFFFFFull) return GSV_E_INVALID_ARG;
+    if (n == 0) return GSV_SUCCESS;
+    if (!key_offsets_ok(pub, pub_off, n)) return GSV_E_INVALID_ARG;
+    std::vector<uint8_t> rows(n * 65), len(n);
+    gsv::pubkey_pack(pub, pub_off, n, rows.data(), len.data());
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    Layout L;
+    const VerifyStage p(L, n);
+    int rc = arena_reserve(c, L.n);
+    if (rc) return rc;
+    uint8_t *d_msg = p.msg(c->arena), *d_sig = p.sig(c->arena), *d_pub = p.pub(c->arena);
+    uint8_t *d_len = p.len(c->arena), *d_ok = p.ok(c->arena);
+    HIPCHK(hipMemcpyAsync(d_msg, msg32, n * 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_sig, sig64, n * 64, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_pub, rows.data(), n * 65, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_len, len.data(), n, hipMemcpyHostToDevice, c->stream));
+    rc = gsv_ecdsa_verify_batch_dev(c, d_msg, d_sig, d_pub, d_len, n, d_ok, c->stream);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return GSV_SUCCESS;
+}
+
+int gsv_pubkey_parse_batch(gsv_ctx* c, const uint8_t* pub, const uint64_t* pub_off, size_t n, uint8_t* pub65_out,
+                           uint8_t* ok) {
+    if (!c || (n && (!pub_off || !pub65_out || !ok)) || n > 0xFFFFFFFFull) return GSV_E_INVALID_ARG;
+    if (n == 0) return GSV_SUCCESS;
+    if (!key_offsets_ok(pub, pub_off, n)) return GSV_E_INVALID_ARG;
+    std::vector<uint8_t> rows(n * 65), len(n);
+    gsv::pubkey_pack(pub, pub_off, n, rows.data(), len.data());
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    Layout L;
+    const PubkeyParseStage p(L, n);
+    int rc = arena_reserve(c, L.n);
+    if (rc) return rc;
+    uint8_t *d_pub = p.pub(c->arena), *d_len = p.len(c->arena), *d_out = p.out(c->arena), *d_ok = p.ok(c->arena);
+    HIPCHK(hipMemcpyAsync(d_pub, rows.data(), n * 65, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_len, len.data(), n, hipMemcpyHostToDevice, c->stream));
+    rc = gsv_pubkey_parse_batch_dev(c, d_pub, d_len, n, d_out, d_ok, c->stream);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(pub65_out, d_out, n * 65, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return GSV_SUCCESS;
 }

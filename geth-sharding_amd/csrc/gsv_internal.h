@@ -19,6 +19,12 @@ hipError_t launch_ecrecover_precompile(const uint8_t* in128, uint32_t n, const u
 hipError_t launch_synth_sign(uint64_t seed, uint32_t n, const uint4* gtab, uint8_t* msg32,
                              uint8_t* sig65, uint8_t* pub65, uint8_t* addr20, hipStream_t st);
 
+// ecverify.hip: keys as n x 65-byte rows plus a length byte each (pubkey_pack.h)
+hipError_t launch_ecverify(const uint8_t* msg32, const uint8_t* sig64, const uint8_t* pub65, const uint8_t* publen,
+                           uint32_t n, const uint4* gtab, uint8_t* ok, hipStream_t st);
+hipError_t launch_pubkey_parse(const uint8_t* pub65, const uint8_t* publen, uint32_t n, uint8_t* out65, uint8_t* ok,
+                               hipStream_t st);
+
 // keccak.hip
 hipError_t launch_keccak256(const uint8_t* data, const uint64_t* off, uint32_t n, uint8_t* out32,
                             hipStream_t st);

@@ -1,5 +1,6 @@
 // secp256k1 public-key recovery core shared by the ecrecover, sender and notary kernels.
-// See ecrecover.hip for the algorithm and the reference semantics it restates.
+// See ecrecover.hip for the algorithm and the reference semantics it restates.  Its scalar
+// multiplications (glv_mul_point, comb_mul_g9) also serve the verification kernel (ecverify.hip).
 #pragma once
 #include "gsv_internal.h"
 #include "keccak_dev.cuh"
@@ -62,7 +63,8 @@ static_assert(GLV_W >= 3 && GLV_W <= 5, "GLV window width");
 constexpr int GLV_LNT = 4;  // entries in LDS
 static_assert(GLV_LNT <= GLV_NT, "LDS holds at most four entries at two waves per SIMD");
 // LDS part: 18 GLV_LNT words per lane, lane-minor ([word][GSV_LTAB_STRIDE]); the kernels that call
-// recover_core run 256-thread blocks and declare __shared__ uint32_t[GSV_LTAB_WORDS].
+// glv_mul_point (through recover_core or verify_core) run 256-thread blocks and declare
+// __shared__ uint32_t[GSV_LTAB_WORDS].
 constexpr int GSV_LTAB_STRIDE = 256;
 constexpr int GSV_LTAB_WORDS = 18 * GLV_LNT * GSV_LTAB_STRIDE;
 // Measured and not kept (r02-r05): the lambda half's x coordinates (beta x_e) precomputed per entry in
@@ -458,53 +460,13 @@ GSV_DI void glv_make_odd(sc& k1, sc& k2) {
     sc_add(k2, k2, B);
 }
 
-// ---------------------------------------------------------------------------- recovery core
-// Returns GSV_ST_OK or GSV_ST_RECOVER_FAILED; on OK (qx, qy) is the affine public key.
-// msg/r/s are 256-bit values as little-endian limbs; recid in 0..3.
-GSV_DI uint32_t recover_core(fe& qx, fe& qy, const uint32_t msg[8], const uint32_t r[8],
-                             const uint32_t s[8], uint32_t recid, const uint4* __restrict__ gtab,
-                             uint32_t* __restrict__ ltab) {
-    bool ok = limbs_lt(r, SN) && limbs_lt(s, SN);
-    sc rs, ss, m;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        rs.v[i] = r[i];
-        ss.v[i] = s[i];
-    }
-    ok = ok && !sc_is_zero(rs) && !sc_is_zero(ss);
-    sc_cond_sub_n(m.v, msg, 0);  // msg mod n (msg < 2^256 < 2n)
-
-    // x = r (+ n when recid & 2; fails for r >= p - n)
-    fe9 x;
-    {
-        bool hi = (recid & 2u) != 0;
-        ok = ok && (!hi || limbs_lt(r, P_MINUS_N));
-        uint32_t xw[8];
-        uint64_t c = 0;
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            c = (uint64_t)r[i] + (hi ? SN[i] : 0u) + hi32(c);
-            xw[i] = lo32(c);
-        }
-        fe9_from_words(x, xw);
-    }
-    fe9 y, t;
-    // R on E_t (see recover_tail_twisted): (c x, c^2), c = x^3 + 7; the root is taken at the end
-    fe9 c;
-    fe9_sqr(t, x);
-    fe9_mul(c, t, x);
-    c.v[0] += 7u;
-    fe9_mul(t, c, x);
-    fe9_sqr(y, c);
-    x = t;
-    // u1 = -m / r, u2 = s / r
-    sc rn, u1, u2;
-    modinv30_words(rn.v, rs.v, MI30_N);  // r^-1 mod n (safegcd; r != 0 on every valid path)
-    sc_mul(u1, rn, m);
-    sc_neg(u1, u1);
-    sc_mul(u2, rn, ss);
-
-    // ---- u2 * R via GLV + fixed w = GLV_W odd digits
+// ---------------------------------------------------------------------------- u2 * P
+// out = u2 * (x, y) via GLV + fixed w = GLV_W odd digits, Jacobian (X, Y, Z magnitude 1);
+// outinf: the ladder ended at the identity.  (x, y), magnitude 1, is a point of order n on any curve
+// y^2 = x^3 + b: recovery's R on its twist (recover_core), verification's parsed key on E
+// (ecverify.hip).  ltab: this lane's column of the block's LDS table (GSV_LTAB_LANE).
+GSV_DI void glv_mul_point(gej9& out, bool& outinf, const sc& u2, const fe9& x, const fe9& y,
+                          uint32_t* __restrict__ ltab) {
     sc k1, k2;
     sc_split_lambda(k1, k2, u2);
     glv_make_odd(k1, k2);  // both halves odd: the recoding's skews are 0, no correcting adds
@@ -653,7 +615,66 @@ GSV_DI uint32_t recover_core(fe& qx, fe& qy, const uint32_t msg[8], const uint32
     }
 #undef GLV_ENTRY
     gejw_to_gej9(acc, acc);  // (X, W, Z) -> Jacobian, Z magnitude 2
-    fe9_mul(acc.z, acc.z, zfac);  // back from E'' to E_t (2*1 -> 1)
+    fe9_mul(out.z, acc.z, zfac);  // back from E'' to the curve of (x, y) (2*1 -> 1)
+    out.x = acc.x;
+    out.y = acc.y;
+    outinf = ainf;
+#undef GLV_SET
+#undef GLV_Y
+#undef GLV_X
+#undef GLV_L
+}
+
+// ---------------------------------------------------------------------------- recovery core
+// Returns GSV_ST_OK or GSV_ST_RECOVER_FAILED; on OK (qx, qy) is the affine public key.
+// msg/r/s are 256-bit values as little-endian limbs; recid in 0..3.
+GSV_DI uint32_t recover_core(fe& qx, fe& qy, const uint32_t msg[8], const uint32_t r[8],
+                             const uint32_t s[8], uint32_t recid, const uint4* __restrict__ gtab,
+                             uint32_t* __restrict__ ltab) {
+    bool ok = limbs_lt(r, SN) && limbs_lt(s, SN);
+    sc rs, ss, m;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        rs.v[i] = r[i];
+        ss.v[i] = s[i];
+    }
+    ok = ok && !sc_is_zero(rs) && !sc_is_zero(ss);
+    sc_cond_sub_n(m.v, msg, 0);  // msg mod n (msg < 2^256 < 2n)
+
+    // x = r (+ n when recid & 2; fails for r >= p - n)
+    fe9 x;
+    {
+        bool hi = (recid & 2u) != 0;
+        ok = ok && (!hi || limbs_lt(r, P_MINUS_N));
+        uint32_t xw[8];
+        uint64_t c = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            c = (uint64_t)r[i] + (hi ? SN[i] : 0u) + hi32(c);
+            xw[i] = lo32(c);
+        }
+        fe9_from_words(x, xw);
+    }
+    fe9 y, t;
+    // R on E_t (see recover_tail_twisted): (c x, c^2), c = x^3 + 7; the root is taken at the end
+    fe9 c;
+    fe9_sqr(t, x);
+    fe9_mul(c, t, x);
+    c.v[0] += 7u;
+    fe9_mul(t, c, x);
+    fe9_sqr(y, c);
+    x = t;
+    // u1 = -m / r, u2 = s / r
+    sc rn, u1, u2;
+    modinv30_words(rn.v, rs.v, MI30_N);  // r^-1 mod n (safegcd; r != 0 on every valid path)
+    sc_mul(u1, rn, m);
+    sc_neg(u1, u1);
+    sc_mul(u2, rn, ss);
+
+    // ---- u2 * R on E_t
+    gej9 acc;
+    bool ainf;
+    glv_mul_point(acc, ainf, u2, x, y, ltab);
 
     // ---- u1 * G via comb
     gej9 accg;

@@ -54,6 +54,15 @@ struct EcrecoverStage {  // gsv_ecrecover_batch
         : msg(L.buf(n * 32)), sig(L.buf(n * 65)), pub(L.buf(n * 65, want_pub)), addr(L.buf(n * 20, want_addr)),
           st(L.buf(n)) {}
 };
+struct VerifyStage {  // gsv_ecdsa_verify_batch: keys in the device layout (pubkey_pack.h)
+    B8 msg, sig, pub, len, ok;
+    VerifyStage(Layout& L, size_t n)
+        : msg(L.buf(n * 32)), sig(L.buf(n * 64)), pub(L.buf(n * 65)), len(L.buf(n)), ok(L.buf(n)) {}
+};
+struct PubkeyParseStage {  // gsv_pubkey_parse_batch
+    B8 pub, len, out, ok;
+    PubkeyParseStage(Layout& L, size_t n) : pub(L.buf(n * 65)), len(L.buf(n)), out(L.buf(n * 65)), ok(L.buf(n)) {}
+};
 // fixed-size records in, fixed-size results and a status byte out: gsv_ecrecover_precompile_batch
 // (128 -> 32), bn_g1_host (128 or 96 -> 64)
 struct RecordStage {

@@ -680,6 +680,52 @@ def _bn256_scalar_mul_batch_dev(self, in_t, out_t, st_t, stream=None):
     check(_lib.load().gsv_bn256_scalar_mul_batch_dev(self._h, _tptr(in_t), n, _tptr(out_t), _tptr(st_t), sp))
 
 
+def _ecdsa_verify_batch(self, msgs, sigs, pubkeys):
+    """ECDSA verification with known keys (gsv.h gsv_ecdsa_verify_batch, the reference's
+    secp256k1.VerifySignature): msgs (n,32) uint8, sigs (n,64) uint8 [R || S], pubkeys a list of n byte
+    strings of any length (33-byte compressed and 65-byte uncompressed or hybrid keys parse).  Returns
+    ok (n,) uint8: 1 where the signature is valid, in lower-s form, and made by that key."""
+    msgs = np.ascontiguousarray(msgs, np.uint8).reshape(-1, 32)
+    sigs = np.ascontiguousarray(sigs, np.uint8).reshape(-1, 64)
+    n = msgs.shape[0]
+    if sigs.shape[0] != n or len(pubkeys) != n:
+        raise ValueError("msgs, sigs and pubkeys batch sizes differ")
+    ok = np.zeros(n, np.uint8)
+    if n:
+        flat, off = _pack(pubkeys)
+        check(_lib.load().gsv_ecdsa_verify_batch(self._h, _ptr(msgs), _ptr(sigs), _ptr(flat), _ptr(off), n, _ptr(ok)))
+    return ok
+
+
+def _pubkey_parse_batch(self, pubkeys):
+    """Parses and re-encodes public keys (gsv.h gsv_pubkey_parse_batch): returns (pub65 (n,65), ok (n,));
+    pub65[i] = 04 || X || Y where key i parses, a zero row and ok[i] == 0 where it does not."""
+    n = len(pubkeys)
+    out = np.zeros((n, 65), np.uint8)
+    ok = np.zeros(n, np.uint8)
+    if n:
+        flat, off = _pack(pubkeys)
+        check(_lib.load().gsv_pubkey_parse_batch(self._h, _ptr(flat), _ptr(off), n, _ptr(out), _ptr(ok)))
+    return out, ok
+
+
+def _ecdsa_verify_batch_dev(self, msg_t, sig_t, pub_t, len_t, ok_t, stream=None):
+    """torch uint8 CUDA tensors: msg_t (n,32), sig_t (n,64), pub_t (n,65) key rows, len_t (n,) key lengths
+    (33 or 65), ok_t (n,); only enqueues on `stream`."""
+    n = msg_t.shape[0]
+    sp = _sp(stream)
+    check(_lib.load().gsv_ecdsa_verify_batch_dev(self._h, _tptr(msg_t), _tptr(sig_t), _tptr(pub_t), _tptr(len_t), n,
+                                                 _tptr(ok_t), sp))
+
+
+def _pubkey_parse_batch_dev(self, pub_t, len_t, out_t, ok_t, stream=None):
+    """torch uint8 CUDA tensors: pub_t (n,65) key rows, len_t (n,), out_t (n,65), ok_t (n,)."""
+    n = pub_t.shape[0]
+    sp = _sp(stream)
+    check(_lib.load().gsv_pubkey_parse_batch_dev(self._h, _tptr(pub_t), _tptr(len_t), n, _tptr(out_t), _tptr(ok_t),
+                                                 sp))
+
+
 def _prepared_shapes(self):
     cnt = ctypes.c_size_t()
     nb = ctypes.c_size_t()
@@ -689,6 +735,10 @@ def _prepared_shapes(self):
 
 Context.ecrecover_precompile_batch = _ecrecover_precompile_batch
 Context.ecrecover_precompile_batch_dev = _ecrecover_precompile_batch_dev
+Context.ecdsa_verify_batch = _ecdsa_verify_batch
+Context.ecdsa_verify_batch_dev = _ecdsa_verify_batch_dev
+Context.pubkey_parse_batch = _pubkey_parse_batch
+Context.pubkey_parse_batch_dev = _pubkey_parse_batch_dev
 Context.prepared_shapes = _prepared_shapes
 Context.bn256_add_batch = _bn256_add_batch
 Context.bn256_scalar_mul_batch = _bn256_scalar_mul_batch

@@ -79,6 +79,10 @@ SIGNATURES = [
     ("gsv_keccak256_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
     ("gsv_ecrecover_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     ("gsv_ecrecover_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    ("gsv_ecdsa_verify_batch", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    ("gsv_ecdsa_verify_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    ("gsv_pubkey_parse_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    ("gsv_pubkey_parse_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     ("gsv_sender_batch", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_int, _vp, _vp]),
     ("gsv_tx_sender_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, ctypes.c_int, _vp, _vp]),
     ("gsv_chunk_root_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp]),

@@ -7,6 +7,10 @@
     EcrecoverBatch(...)         batch form used by the notary / tx pool hooks
     Keccak256Batch(msgs)        batch form
     Ecrecover precompile        core/vm/contracts.go:70-101 (EcrecoverPrecompile.Run / RunBatch)
+    VerifySignature(pub, hash, sig)   crypto/signature_cgo.go:63-68 -> secp256k1.VerifySignature
+    VerifySignatureBatch(...)   batch form
+    DecompressPubkey(pub33)     crypto/signature_cgo.go:71-77 (returns the 65-byte key here)
+    CompressPubkey(pub65)       crypto/signature_cgo.go:80-82
 
 Errors mirror crypto/secp256k1/secp256.go:54-62 and are raised as exceptions.
 """
@@ -73,6 +77,62 @@ def EcrecoverBatch(hashes, sigs, want_pub=True, want_addr=False, ctx=None):
     """Batch ecrecover: per-item status codes (GSV_ST_*) instead of exceptions."""
     return (ctx or default_context()).ecrecover_batch(hashes, sigs, want_pub=want_pub,
                                                       want_addr=want_addr)
+
+
+class ErrInvalidPubkey(ValueError):
+    """invalid public key"""
+
+
+def VerifySignature(pubkey: bytes, hash: bytes, sig: bytes, ctx=None) -> bool:
+    """crypto/signature_cgo.go:63-68 -> secp256k1.VerifySignature (secp256.go:124-134): whether `sig`
+    ([R || S], 64 bytes, no recovery id) is a valid lower-s signature of `hash` by `pubkey` (33 or 65
+    bytes).  The three length rules come first and need no GPU."""
+    pubkey, hash, sig = bytes(pubkey), bytes(hash), bytes(sig)
+    if len(hash) != 32 or len(sig) != 64 or len(pubkey) == 0:
+        return False
+    ok = (ctx or default_context()).ecdsa_verify_batch(np.frombuffer(hash, np.uint8)[None],
+                                                       np.frombuffer(sig, np.uint8)[None], [pubkey])
+    return bool(ok[0])
+
+
+def VerifySignatureBatch(pubkeys, hashes, sigs, ctx=None) -> np.ndarray:
+    """Batch VerifySignature: a bool per item.  An item with a hash that is not 32 bytes, a signature
+    that is not 64 bytes or an empty key is False, as VerifySignature makes it; the rest go to the GPU in
+    one call."""
+    pubkeys = [bytes(k) for k in pubkeys]
+    hashes = [bytes(h) for h in hashes]
+    sigs = [bytes(s) for s in sigs]
+    n = len(pubkeys)
+    if len(hashes) != n or len(sigs) != n:
+        raise ValueError("pubkeys, hashes and sigs batch sizes differ")
+    out = np.zeros(n, bool)
+    idx = [i for i in range(n) if len(hashes[i]) == 32 and len(sigs[i]) == 64 and len(pubkeys[i]) != 0]
+    if idx:
+        msg = np.frombuffer(b"".join(hashes[i] for i in idx), np.uint8).reshape(-1, 32)
+        sg = np.frombuffer(b"".join(sigs[i] for i in idx), np.uint8).reshape(-1, 64)
+        ok = (ctx or default_context()).ecdsa_verify_batch(msg, sg, [pubkeys[i] for i in idx])
+        out[idx] = ok != 0
+    return out
+
+
+def DecompressPubkey(pubkey: bytes, ctx=None) -> bytes:
+    """crypto/signature_cgo.go:71-77: the 65-byte uncompressed form of a 33-byte compressed key."""
+    pubkey = bytes(pubkey)
+    if len(pubkey) != 33:  # secp256k1.DecompressPubkey returns (nil, nil) before any parsing
+        raise ErrInvalidPubkey("invalid public key")
+    pub, ok = (ctx or default_context()).pubkey_parse_batch([pubkey])
+    if not ok[0]:
+        raise ErrInvalidPubkey("invalid public key")
+    return bytes(pub[0])
+
+
+def CompressPubkey(pubkey: bytes, ctx=None) -> bytes:
+    """crypto/signature_cgo.go:80-82: 02 | 03 followed by X.  The reference panics on a key that does not
+    parse; here that raises ErrInvalidPubkey."""
+    pub, ok = (ctx or default_context()).pubkey_parse_batch([bytes(pubkey)])
+    if not ok[0]:
+        raise ErrInvalidPubkey("invalid public key")
+    return bytes([2 | (int(pub[0, 64]) & 1)]) + bytes(pub[0, 1:33])
 
 
 def PubkeyToAddress(pub65: bytes) -> bytes:

@@ -10,6 +10,11 @@
  *   gsv_ecrecover_batch        <- secp256k1_ext_ecdsa_recover (crypto/secp256k1/ext.h:30-47)
  *                                 via secp256k1.RecoverPubkey (crypto/secp256k1/secp256.go:105-122)
  *                                 / crypto.Ecrecover (crypto/signature_cgo.go:31)
+ *   gsv_ecdsa_verify_batch     <- secp256k1_ext_ecdsa_verify (crypto/secp256k1/ext.h) via
+ *                                 secp256k1.VerifySignature (crypto/secp256k1/secp256.go:124-134)
+ *                                 / crypto.VerifySignature (crypto/signature_cgo.go:63-68)
+ *   gsv_pubkey_parse_batch     <- secp256k1_ext_reencode_pubkey (crypto/secp256k1/ext.h) via
+ *                                 DecompressPubkey / CompressPubkey (secp256.go:136-169)
  *   gsv_sender_batch           <- recoverPlain (core/types/transaction_signing.go:222-247)
  *                                 + crypto.ValidateSignatureValues (crypto/crypto.go:181-192)
  *   gsv_tx_sender_batch        <- types.Sender(signer, tx) (core/types/transaction_signing.go:72-89,
@@ -185,6 +190,34 @@ int gsv_ecrecover_batch(gsv_ctx *ctx, const uint8_t *msg32, const uint8_t *sig65
 int gsv_ecrecover_batch_dev(gsv_ctx *ctx, const uint8_t *d_msg32, const uint8_t *d_sig65, size_t n,
                             uint8_t *d_pub65_out, uint8_t *d_addr20_out, uint8_t *d_status,
                             void *stream);
+
+/* ---- ECDSA verification with a known key, and public-key parsing ----
+ * The cgo path's semantics (crypto/secp256k1/ext.h, secp256.go:124-169), not signature_nocgo.go's.
+ * msg32: n x 32 B hashes; sig64: n x 64 B [R || S]; key i = pub[pub_off[i] .. pub_off[i+1]), any length.
+ * ok[i] = 1 iff all of
+ *   - r, s in [1, n) (a value >= n is invalid, not reduced) and s <= n/2 (the malleability rule);
+ *   - the key parses (eckey_pubkey_parse): 33 bytes 02|03 || X with X < p, X^3 + 7 a square, Y of that
+ *     parity; or 65 bytes 04|06|07 || X || Y with X, Y < p, Y^2 = X^3 + 7 and, for 06|07, Y of the
+ *     prefix's parity; every other length or prefix is invalid;
+ *   - with m = msg mod n (m = 0 is allowed), X = (m/s) G + (r/s) P is not the identity and its x
+ *     coordinate is r, or r + n when r < p - n.
+ * Else ok[i] = 0: an item never fails the batch.
+ * gsv_pubkey_parse_batch applies the key rule alone and re-encodes: pub65_out[i] = 04 || X || Y
+ * (canonical) and ok[i] = 1, or 65 zero bytes and ok[i] = 0 (secp256k1_ext_reencode_pubkey with a
+ * 65-byte output: DecompressPubkey; CompressPubkey is its first 33 bytes with 02 | (Y & 1)). */
+int gsv_ecdsa_verify_batch(gsv_ctx *ctx, const uint8_t *msg32, const uint8_t *sig64, const uint8_t *pub,
+                           const uint64_t *pub_off, size_t n, uint8_t *ok);
+int gsv_pubkey_parse_batch(gsv_ctx *ctx, const uint8_t *pub, const uint64_t *pub_off, size_t n,
+                           uint8_t *pub65_out, uint8_t *ok);
+/* Device-resident forms.  Keys in the device layout: d_pub65 = n rows of 65 B (a 33-byte key in the
+ * first 33 bytes of its row; the rest of that row is not read as key material), d_publen = n length
+ * bytes, 33 or 65 (any other value: an invalid key, as the host forms give every other length).  They
+ * only enqueue (one launch) on `stream` (NULL = the context stream).  No prepare call. */
+int gsv_ecdsa_verify_batch_dev(gsv_ctx *ctx, const uint8_t *d_msg32, const uint8_t *d_sig64,
+                               const uint8_t *d_pub65, const uint8_t *d_publen, size_t n, uint8_t *d_ok,
+                               void *stream);
+int gsv_pubkey_parse_batch_dev(gsv_ctx *ctx, const uint8_t *d_pub65, const uint8_t *d_publen, size_t n,
+                               uint8_t *d_pub65_out, uint8_t *d_ok, void *stream);
 
 /* ---- the ecrecover precompile (core/vm/contracts.go:78-101) ----
  * Input i = in[off[i] .. off[i+1]) = hash(32) || v(32) || r(32) || s(32), right-padded with zeros to
