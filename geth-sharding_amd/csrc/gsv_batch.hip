@@ -1,5 +1,5 @@
 // Stateless batches of the C ABI (gsv_ctx.h): Keccak-256, ecrecover and its precompile, ECDSA
-// verification and public-key parsing, bn256Add / bn256ScalarMul, recoverPlain over decoded fields,
+// verification and public-key parsing, crypto.Sign and public-key derivation, bn256Add / bn256ScalarMul, recoverPlain over decoded fields,
 // the synthetic signer, types.Sender over tx RLP.
 #include <thread>
 
@@ -156,6 +156,99 @@ int gsv_pubkey_parse_batch(gsv_ctx* c, const uint8_t* pub, const uint64_t* pub_o
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(pub65_out, d_out, n * 65, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return GSV_SUCCESS;
+}
+
+// ------------------------------------------------------------------ crypto.Sign, public-key derivation
+int gsv_ecdsa_sign_batch_dev(gsv_ctx* c, const uint8_t* d_msg32, const uint8_t* d_seckey32, size_t n,
+                             uint8_t* d_sig65_out, uint8_t* d_status, void* stream) {
+    if (!c || (n && (!d_msg32 || !d_seckey32 || !d_sig65_out || !d_status)) || n > 0xFFFFFFFFull)
+        return GSV_E_INVALID_ARG;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    KTimer t(c, GSV_K_ECRECOVER, st);
+    return hip_err(gsv::launch_ecsign(d_msg32, d_seckey32, (uint32_t)n, c->gtab, d_sig65_out, d_status, st));
+}
+
+int gsv_pubkey_create_batch_dev(gsv_ctx* c, const uint8_t* d_seckey32, size_t n, uint8_t* d_pub65_out,
+                                uint8_t* d_addr20_out, uint8_t* d_status, void* stream) {
+    if (!c || (n && (!d_seckey32 || !d_pub65_out || !d_status)) || n > 0xFFFFFFFFull) return GSV_E_INVALID_ARG;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    KTimer t(c, GSV_K_ECRECOVER, st);
+    return hip_err(gsv::launch_pubkey_create(d_seckey32, (uint32_t)n, c->gtab, d_pub65_out, d_addr20_out, d_status,
+                                             st));
+}
+
+// The staged secret keys of a host form: overwritten on the context stream, and the stream waited
+// for, on every way out of the scope that follows the copy-in (HIPCHK's early returns included).
+// finish() is the success path's last step and reports the two calls' outcome.
+struct SecretWipe {
+    gsv_ctx* c;
+    uint8_t* p;
+    size_t bytes;
+    bool done = false;
+    int finish() {
+        done = true;
+        hipError_t a = hipMemsetAsync(p, 0, bytes, c->stream);
+        hipError_t b = hipStreamSynchronize(c->stream);
+        return hip_err(a != hipSuccess ? a : b);
+    }
+    ~SecretWipe() {
+        if (!done) finish();
+    }
+};
+
+int gsv_ecdsa_sign_batch(gsv_ctx* c, const uint8_t* msg32, const uint8_t* seckey32, size_t n, uint8_t* sig65_out,
+                         uint8_t* status) {
+    if (!c || (n && (!msg32 || !seckey32 || !sig65_out || !status)) || n > 0xFFFFFFFFull) return GSV_E_INVALID_ARG;
+    if (n == 0) return GSV_SUCCESS;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    Layout L;
+    const SignStage p(L, n);
+    int rc = arena_reserve(c, L.n);
+    if (rc) return rc;
+    uint8_t *d_key = p.key(c->arena), *d_msg = p.msg(c->arena), *d_sig = p.sig(c->arena), *d_st = p.st(c->arena);
+    SecretWipe wipe{c, d_key, n * 32};  // from here on the keys may be in HBM
+    HIPCHK(hipMemcpyAsync(d_key, seckey32, n * 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_msg, msg32, n * 32, hipMemcpyHostToDevice, c->stream));
+    rc = gsv_ecdsa_sign_batch_dev(c, d_msg, d_key, n, d_sig, d_st, c->stream);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(sig65_out, d_sig, n * 65, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, c->stream));
+    return wipe.finish();
+}
+
+int gsv_pubkey_create_batch(gsv_ctx* c, const uint8_t* seckey32, size_t n, uint8_t* pub65_out, uint8_t* addr20_out,
+                            uint8_t* status) {
+    if (!c || (n && (!seckey32 || !pub65_out || !status)) || n > 0xFFFFFFFFull) return GSV_E_INVALID_ARG;
+    if (n == 0) return GSV_SUCCESS;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    Layout L;
+    const PubkeyCreateStage p(L, n, addr20_out != nullptr);
+    int rc = arena_reserve(c, L.n);
+    if (rc) return rc;
+    uint8_t *d_key = p.key(c->arena), *d_pub = p.pub(c->arena), *d_st = p.st(c->arena);
+    uint8_t* d_addr = p.addr(c->arena);  // nullptr when not asked for
+    SecretWipe wipe{c, d_key, n * 32};
+    HIPCHK(hipMemcpyAsync(d_key, seckey32, n * 32, hipMemcpyHostToDevice, c->stream));
+    rc = gsv_pubkey_create_batch_dev(c, d_key, n, d_pub, d_addr, d_st, c->stream);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(pub65_out, d_pub, n * 65, hipMemcpyDeviceToHost, c->stream));
+    if (addr20_out) HIPCHK(hipMemcpyAsync(addr20_out, d_addr, n * 20, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, c->stream));
+    return wipe.finish();
+}
+
+// Test hook of the rule above: bytes [off, off + n) of the context's staging arena, as they are now.
+int gsv_ctx_arena_read(gsv_ctx* c, size_t off, size_t n, uint8_t* out) {
+    if (!c || (n && !out)) return GSV_E_INVALID_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (off > c->arena_cap || n > c->arena_cap - off) return GSV_E_INVALID_ARG;
+    if (n == 0) return GSV_SUCCESS;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(out, c->arena + off, n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return GSV_SUCCESS;
 }

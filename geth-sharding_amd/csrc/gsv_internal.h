@@ -25,6 +25,12 @@ hipError_t launch_ecverify(const uint8_t* msg32, const uint8_t* sig64, const uin
 hipError_t launch_pubkey_parse(const uint8_t* pub65, const uint8_t* publen, uint32_t n, uint8_t* out65, uint8_t* ok,
                                hipStream_t st);
 
+// ecsign.hip: crypto.Sign (RFC 6979 nonce) and secp256k1_ec_pubkey_create; status GSV_ST_OK / GSV_ST_INVALID_KEY
+hipError_t launch_ecsign(const uint8_t* msg32, const uint8_t* seckey32, uint32_t n, const uint4* gtab, uint8_t* sig65,
+                         uint8_t* status, hipStream_t st);
+hipError_t launch_pubkey_create(const uint8_t* seckey32, uint32_t n, const uint4* gtab, uint8_t* pub65,
+                                uint8_t* addr20, uint8_t* status, hipStream_t st);
+
 // keccak.hip
 hipError_t launch_keccak256(const uint8_t* data, const uint64_t* off, uint32_t n, uint8_t* out32,
                             hipStream_t st);

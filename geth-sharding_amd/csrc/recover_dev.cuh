@@ -733,20 +733,13 @@ GSV_DI void derive32(uint32_t out_be_limbs[8], uint64_t seed, uint64_t i, uint32
     }
 }
 
-// ECDSA signature with explicit nonce, low-s normalised (libsecp256k1 semantics); d, k are
-// reduced mod n here (0 -> 1).  (px, py) = d*G.  m = message as limbs (any 256-bit value).
-GSV_DI void ecdsa_sign(uint32_t r_out[8], uint32_t s_out[8], uint32_t& recid, fe& px, fe& py, sc d, sc k,
-                       const uint32_t m[8], const uint4* __restrict__ gtab) {
-    sc_cond_sub_n(d.v, d.v, 0);
-    sc_cond_sub_n(k.v, k.v, 0);
-    if (sc_is_zero(d)) d.v[0] = 1;
-    if (sc_is_zero(k)) k.v[0] = 1;
-    sc mr;
-    sc_cond_sub_n(mr.v, m, 0);
-    gej9 P;
-    bool pinf;
-    comb_mul_g9(P, pinf, d, gtab);
-    gej9_to_affine_words(px, py, P);
+// The signature itself (libsecp256k1/src/ecdsa_impl.h secp256k1_ecdsa_sig_sign): R = k G, r = R.x mod n,
+// s = (m + r d) / k, low-s normalised, recid = (R.x >= n ? 2 : 0) | (R.y odd), bit 0 flipped with s.
+// d, k in [1, n), m = the message as limbs (any 256-bit value; reduced here, where s needs it).  One comb
+// multiplication.  r or s may come out zero: the caller's to test (crypto.Sign's retry; the synthetic
+// signer does not).
+GSV_DI void ecdsa_sign_core(uint32_t r_out[8], uint32_t s_out[8], uint32_t& recid, const sc& d, const sc& k,
+                            const uint32_t m[8], const uint4* __restrict__ gtab) {
     gej9 R;
     bool rinf;
     comb_mul_g9(R, rinf, k, gtab);
@@ -758,8 +751,9 @@ GSV_DI void ecdsa_sign(uint32_t r_out[8], uint32_t s_out[8], uint32_t& recid, fe
     sc_cond_sub_n(r.v, rx.v, 0);
     if (over) recid |= 2u;
     // s = k^-1 (m + r d)
-    sc kinv, s, t;
+    sc kinv, s, t, mr;
     modinv30_words_ct(kinv.v, k.v, MI30_N);  // the nonce is secret: constant-time divsteps
+    sc_cond_sub_n(mr.v, m, 0);               // msg mod n (msg < 2^256 < 2n)
     sc_mul(t, r, d);
     sc_add(t, t, mr);
     sc_mul(s, kinv, t);
@@ -772,6 +766,21 @@ GSV_DI void ecdsa_sign(uint32_t r_out[8], uint32_t s_out[8], uint32_t& recid, fe
         r_out[i] = r.v[i];
         s_out[i] = s.v[i];
     }
+}
+
+// The synthetic signer's signature with an explicit nonce: d, k are reduced mod n here (0 -> 1, this
+// signer's rule alone).  (px, py) = d*G.  m = message as limbs (any 256-bit value).
+GSV_DI void ecdsa_sign(uint32_t r_out[8], uint32_t s_out[8], uint32_t& recid, fe& px, fe& py, sc d, sc k,
+                       const uint32_t m[8], const uint4* __restrict__ gtab) {
+    sc_cond_sub_n(d.v, d.v, 0);
+    sc_cond_sub_n(k.v, k.v, 0);
+    if (sc_is_zero(d)) d.v[0] = 1;
+    if (sc_is_zero(k)) k.v[0] = 1;
+    gej9 P;
+    bool pinf;
+    comb_mul_g9(P, pinf, d, gtab);
+    gej9_to_affine_words(px, py, P);
+    ecdsa_sign_core(r_out, s_out, recid, d, k, m, gtab);
 }
 
 }  // namespace gsv

@@ -63,6 +63,17 @@ struct PubkeyParseStage {  // gsv_pubkey_parse_batch
     B8 pub, len, out, ok;
     PubkeyParseStage(Layout& L, size_t n) : pub(L.buf(n * 65)), len(L.buf(n)), out(L.buf(n * 65)), ok(L.buf(n)) {}
 };
+// gsv_ecdsa_sign_batch, gsv_pubkey_create_batch.  The secret keys come FIRST, so the region the host
+// form overwrites before it returns is [key.off, key.off + key.bytes) whatever else is staged.
+struct SignStage {
+    B8 key, msg, sig, st;
+    SignStage(Layout& L, size_t n) : key(L.buf(n * 32)), msg(L.buf(n * 32)), sig(L.buf(n * 65)), st(L.buf(n)) {}
+};
+struct PubkeyCreateStage {
+    B8 key, pub, addr, st;
+    PubkeyCreateStage(Layout& L, size_t n, bool want_addr)
+        : key(L.buf(n * 32)), pub(L.buf(n * 65)), addr(L.buf(n * 20, want_addr)), st(L.buf(n)) {}
+};
 // fixed-size records in, fixed-size results and a status byte out: gsv_ecrecover_precompile_batch
 // (128 -> 32), bn_g1_host (128 or 96 -> 64)
 struct RecordStage {

@@ -726,6 +726,67 @@ def _pubkey_parse_batch_dev(self, pub_t, len_t, out_t, ok_t, stream=None):
                                                  sp))
 
 
+def _seckey_rows(keys):
+    keys = np.ascontiguousarray(keys, np.uint8)
+    if keys.size % 32:
+        raise ValueError("secret keys are 32 bytes each")
+    return keys.reshape(-1, 32)
+
+
+def _ecdsa_sign_batch(self, msgs, keys):
+    """crypto.Sign over a batch (gsv.h gsv_ecdsa_sign_batch): msgs (n,32) uint8 hashes, keys (n,32) uint8
+    big-endian secret keys.  Returns (sig65 (n,65) [R || S || recid], status (n,)); status[i] ==
+    ST_INVALID_KEY and a zero row for a key of 0 or >= n.  The keys' device copy is overwritten before the
+    call returns; the arrays passed in stay the caller's to wipe."""
+    msgs = np.ascontiguousarray(msgs, np.uint8).reshape(-1, 32)
+    keys = _seckey_rows(keys)
+    n = msgs.shape[0]
+    if keys.shape[0] != n:
+        raise ValueError("msgs and keys batch sizes differ")
+    sig = np.zeros((n, 65), np.uint8)
+    st = np.zeros(n, np.uint8)
+    if n:
+        check(_lib.load().gsv_ecdsa_sign_batch(self._h, _ptr(msgs), _ptr(keys), n, _ptr(sig), _ptr(st)))
+    return sig, st
+
+
+def _pubkey_create_batch(self, keys, want_addr=False):
+    """Public keys of secret keys (gsv.h gsv_pubkey_create_batch): returns (pub65 (n,65), addr20 (n,20) or
+    None, status (n,)); a zero row and ST_INVALID_KEY for a key of 0 or >= n."""
+    keys = _seckey_rows(keys)
+    n = keys.shape[0]
+    pub = np.zeros((n, 65), np.uint8)
+    addr = np.zeros((n, 20), np.uint8) if want_addr else None
+    st = np.zeros(n, np.uint8)
+    if n:
+        check(_lib.load().gsv_pubkey_create_batch(self._h, _ptr(keys), n, _ptr(pub),
+                                                  _ptr(addr) if want_addr else None, _ptr(st)))
+    return pub, addr, st
+
+
+def _ecdsa_sign_batch_dev(self, msg_t, key_t, sig_t, st_t, stream=None):
+    """torch uint8 CUDA tensors: msg_t (n,32), key_t (n,32) secret keys, sig_t (n,65), st_t (n,); only
+    enqueues on `stream`.  key_t is the caller's to wipe."""
+    n = msg_t.shape[0]
+    sp = _sp(stream)
+    check(_lib.load().gsv_ecdsa_sign_batch_dev(self._h, _tptr(msg_t), _tptr(key_t), n, _tptr(sig_t), _tptr(st_t), sp))
+
+
+def _pubkey_create_batch_dev(self, key_t, pub_t, addr_t, st_t, stream=None):
+    """torch uint8 CUDA tensors: key_t (n,32), pub_t (n,65), addr_t (n,20) or None, st_t (n,)."""
+    n = key_t.shape[0]
+    sp = _sp(stream)
+    check(_lib.load().gsv_pubkey_create_batch_dev(self._h, _tptr(key_t), n, _tptr(pub_t),
+                                                  _tptr(addr_t) if addr_t is not None else None, _tptr(st_t), sp))
+
+
+def _arena_read(self, off, n):
+    """Test hook (gsv.h gsv_ctx_arena_read): n bytes of the staging arena from `off`, as they are now."""
+    out = np.zeros(n, np.uint8)
+    check(_lib.load().gsv_ctx_arena_read(self._h, off, n, _ptr(out)))
+    return out
+
+
 def _prepared_shapes(self):
     cnt = ctypes.c_size_t()
     nb = ctypes.c_size_t()
@@ -739,6 +800,11 @@ Context.ecdsa_verify_batch = _ecdsa_verify_batch
 Context.ecdsa_verify_batch_dev = _ecdsa_verify_batch_dev
 Context.pubkey_parse_batch = _pubkey_parse_batch
 Context.pubkey_parse_batch_dev = _pubkey_parse_batch_dev
+Context.ecdsa_sign_batch = _ecdsa_sign_batch
+Context.ecdsa_sign_batch_dev = _ecdsa_sign_batch_dev
+Context.pubkey_create_batch = _pubkey_create_batch
+Context.pubkey_create_batch_dev = _pubkey_create_batch_dev
+Context._arena_read = _arena_read
 Context.prepared_shapes = _prepared_shapes
 Context.bn256_add_batch = _bn256_add_batch
 Context.bn256_scalar_mul_batch = _bn256_scalar_mul_batch

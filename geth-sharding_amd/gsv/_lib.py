@@ -25,6 +25,7 @@ ST_INVALID_PUBKEY = 7
 ST_BAD_RLP = 8
 ST_BN_BAD_INPUT = 9
 ST_PROPOSER_MISMATCH = 10
+ST_INVALID_KEY = 11
 
 SIGNER_EIP155 = 0
 SIGNER_HOMESTEAD = 1
@@ -83,6 +84,11 @@ SIGNATURES = [
     ("gsv_ecdsa_verify_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     ("gsv_pubkey_parse_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
     ("gsv_pubkey_parse_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    ("gsv_ecdsa_sign_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    ("gsv_ecdsa_sign_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    ("gsv_pubkey_create_batch", ctypes.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    ("gsv_pubkey_create_batch_dev", ctypes.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    ("gsv_ctx_arena_read", ctypes.c_int, [_vp, _sz, _sz, _vp]),
     ("gsv_sender_batch", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_int, _vp, _vp]),
     ("gsv_tx_sender_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, ctypes.c_int, _vp, _vp]),
     ("gsv_chunk_root_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp]),

@@ -11,6 +11,9 @@
     VerifySignatureBatch(...)   batch form
     DecompressPubkey(pub33)     crypto/signature_cgo.go:71-77 (returns the 65-byte key here)
     CompressPubkey(pub65)       crypto/signature_cgo.go:80-82
+    Sign(hash, prv)             crypto/signature_cgo.go:54-61 -> secp256k1.Sign (secp256.go:70-99)
+    SignBatch(hashes, keys)     batch form: per-item status codes
+    PubkeyFromSeckey(prv)       secp256k1_ec_pubkey_create, the derivation behind crypto.ToECDSA
 
 Errors mirror crypto/secp256k1/secp256.go:54-62 and are raised as exceptions.
 """
@@ -133,6 +136,53 @@ def CompressPubkey(pubkey: bytes, ctx=None) -> bytes:
     if not ok[0]:
         raise ErrInvalidPubkey("invalid public key")
     return bytes([2 | (int(pub[0, 64]) & 1)]) + bytes(pub[0, 1:33])
+
+
+class ErrInvalidKey(ValueError):
+    """invalid private key"""
+
+
+def _padded_key(prv) -> bytes:
+    """math.PaddedBigBytes(prv.D, 32) (crypto/signature_cgo.go:58): an int, or bytes of at most 32, as 32
+    big-endian bytes.  What has no such form is no valid key."""
+    if isinstance(prv, int):
+        if prv < 0 or prv >> 256:
+            raise ErrInvalidKey("invalid private key")
+        return prv.to_bytes(32, "big")
+    prv = bytes(prv)
+    if len(prv) > 32:
+        raise ErrInvalidKey("invalid private key")
+    return prv.rjust(32, b"\0")
+
+
+def SignBatch(hashes, keys, ctx=None):
+    """Batch crypto.Sign: hashes (n,32) uint8, keys (n,32) uint8 big-endian secret keys.  Returns
+    (sigs (n,65) [R || S || V], status (n,)): ST_INVALID_KEY and a zero row for a key of 0 or >= n."""
+    return (ctx or default_context()).ecdsa_sign_batch(hashes, keys)
+
+
+def Sign(hash: bytes, prv, ctx=None) -> bytes:
+    """crypto/signature_cgo.go:54-61 -> secp256k1.Sign (secp256.go:70-99): the 65-byte [R || S || V]
+    signature of `hash` (32 bytes) by the secret key `prv` (an int, or up to 32 big-endian bytes), V in
+    {0, 1}, with RFC 6979's nonce: byte for byte the reference's."""
+    hash = bytes(hash)
+    if len(hash) != 32:
+        raise ErrInvalidMsgLen("invalid message length, need 32 bytes")
+    key = _padded_key(prv)
+    sig, st = SignBatch(np.frombuffer(hash, np.uint8)[None], np.frombuffer(key, np.uint8)[None], ctx)
+    if st[0] != _lib.ST_OK:
+        raise ErrInvalidKey("invalid private key")
+    return bytes(sig[0])
+
+
+def PubkeyFromSeckey(prv, ctx=None) -> bytes:
+    """The 65-byte public key 04 || X || Y of a secret key (secp256k1_ec_pubkey_create, what
+    crypto.ToECDSA derives)."""
+    key = _padded_key(prv)
+    pub, _, st = (ctx or default_context()).pubkey_create_batch(np.frombuffer(key, np.uint8)[None])
+    if st[0] != _lib.ST_OK:
+        raise ErrInvalidKey("invalid private key")
+    return bytes(pub[0])
 
 
 def PubkeyToAddress(pub65: bytes) -> bytes:

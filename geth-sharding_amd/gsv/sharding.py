@@ -9,6 +9,7 @@ batched on the GPU.
     VerifyProposerSignatures(hdrs)   proposer signature over the unsigned header hash, as made by
                                      SMCClient.Sign (sharding/mainchain/smc_client.go:245-248) at
                                      sharding/proposer/proposer.go:83 (the reference never checks it)
+    SignHeaders(hdrs, keys)          that signature made: crypto.Sign over each unsigned header hash
 
 Integers (ShardID, Period) are Python ints (the reference's *big.Int); None stands for a nil pointer.
 """
@@ -115,6 +116,29 @@ def VerifyProposerSignatures(headers, ctx=None):
     never recovered: GSV_ST_INVALID_SIG_LEN (secp256k1.ErrInvalidSignatureLen) and a zero signer."""
     _, signer, st = (ctx or default_context()).collation_header_verify_batch(*_pack_headers(headers))
     return signer, st
+
+
+def SignHeaders(headers, keys, ctx=None):
+    """The proposer's half of VerifyProposerSignatures: signs each header as createCollation does
+    (sharding/proposer/proposer.go:83: SMCClient.Sign -> keystore.SignHash -> crypto.Sign over the
+    header's hash with ProposerSignature empty) and AddSig's the 65-byte signature.  keys[i]: header i's
+    secret key, an int or up to 32 big-endian bytes.  One batch of header hashes and one of signatures on
+    the GPU.  A key that is no valid secret key raises crypto.ErrInvalidKey and leaves EVERY header as it
+    was."""
+    from . import crypto
+    headers = list(headers)
+    keys = [crypto._padded_key(k) for k in keys]
+    if len(keys) != len(headers):
+        raise ValueError("headers and keys batch sizes differ")
+    if not headers:
+        return
+    unsigned = [CollationHeader(h.ShardID(), h.ChunkRoot(), h.Period(), h.ProposerAddress(), None) for h in headers]
+    hashes = HeaderHashBatch(unsigned, ctx)
+    sigs, st = crypto.SignBatch(hashes, np.frombuffer(b"".join(keys), np.uint8).reshape(-1, 32), ctx)
+    if (st != _lib.ST_OK).any():
+        raise crypto.ErrInvalidKey("invalid private key (header %d)" % int(np.flatnonzero(st != _lib.ST_OK)[0]))
+    for h, s in zip(headers, sigs):
+        h.AddSig(bytes(s))
 
 
 class Collation:

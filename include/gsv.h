@@ -15,6 +15,11 @@
  *                                 / crypto.VerifySignature (crypto/signature_cgo.go:63-68)
  *   gsv_pubkey_parse_batch     <- secp256k1_ext_reencode_pubkey (crypto/secp256k1/ext.h) via
  *                                 DecompressPubkey / CompressPubkey (secp256.go:136-169)
+ *   gsv_ecdsa_sign_batch       <- secp256k1_ecdsa_sign_recoverable with secp256k1_nonce_function_rfc6979
+ *                                 via secp256k1.Sign (crypto/secp256k1/secp256.go:70-99) / crypto.Sign
+ *                                 (crypto/signature_cgo.go:54-61)
+ *   gsv_pubkey_create_batch    <- secp256k1_ec_pubkey_create (libsecp256k1/src/secp256k1.c), the key
+ *                                 derivation behind crypto.ToECDSA / crypto.PubkeyToAddress
  *   gsv_sender_batch           <- recoverPlain (core/types/transaction_signing.go:222-247)
  *                                 + crypto.ValidateSignatureValues (crypto/crypto.go:181-192)
  *   gsv_tx_sender_batch        <- types.Sender(signer, tx) (core/types/transaction_signing.go:72-89,
@@ -95,6 +100,7 @@ extern "C" {
 #define GSV_ST_BAD_RLP 8           /* rlp decode error of the tx */
 #define GSV_ST_BN_BAD_INPUT 9      /* bn256 unmarshal / curve / subgroup failure */
 #define GSV_ST_PROPOSER_MISMATCH 10 /* recovered signer != header ProposerAddress */
+#define GSV_ST_INVALID_KEY 11      /* secp256k1.ErrInvalidKey          secp256.go:58 */
 
 /* signer kinds for gsv_tx_sender_batch (core/types/transaction_signing.go) */
 #define GSV_SIGNER_EIP155 0
@@ -218,6 +224,44 @@ int gsv_ecdsa_verify_batch_dev(gsv_ctx *ctx, const uint8_t *d_msg32, const uint8
                                void *stream);
 int gsv_pubkey_parse_batch_dev(gsv_ctx *ctx, const uint8_t *d_pub65, const uint8_t *d_publen, size_t n,
                                uint8_t *d_pub65_out, uint8_t *d_ok, void *stream);
+
+/* ---- crypto.Sign and public-key derivation ----
+ * secp256k1.Sign (crypto/secp256k1/secp256.go:70-99): msg32 = n x 32 B hashes, seckey32 = n x 32 B
+ * big-endian secret keys.  A key of 0 or >= n gets status GSV_ST_INVALID_KEY (secp256k1_ec_seckey_verify,
+ * secp256.go:78) and 65 zero bytes.  Else status GSV_ST_OK and sig65_out[i] = [R || S || recid], byte
+ * for byte what the reference returns: the nonce is RFC 6979's (HMAC-SHA256 over key || msg32, the
+ * message as its raw 32 bytes; secp256k1_nonce_function_rfc6979 with no extra data), tried at counter
+ * 0, 1, ... until it is in [1, n) and gives r, s != 0; s is normalised to the low half; recid =
+ * (R.x >= n ? 2 : 0) | (R.y odd), bit 0 flipped when s was negated.  secp256k1.ErrSignFailed has no
+ * status: with this nonce function the reference cannot return it.
+ * gsv_pubkey_create_batch applies the same key rule: pub65_out[i] = 04 || X || Y of key i's point and,
+ * when addr20_out is not NULL, addr20_out[i] = Keccak256(X || Y)[12:32]; zero bytes for an invalid key.
+ *
+ * Secret keys.  The host forms stage the keys in the context's device arena and overwrite that copy,
+ * on the context stream and before their final synchronisation, on every return that follows the
+ * copy-in (error returns included); they keep no host copy.  The _dev forms read the caller's device
+ * buffer and write no key material anywhere; wiping that buffer is the caller's.
+ * What this path does NOT promise (compare crypto/signature_cgo.go:48-51 on its own caveat): the
+ * fixed-base multiplication indexes a 1 GB table in HBM by 20-bit digits of the secret nonce (and, for
+ * key derivation, of the secret key), and the low-s step branches on a bit derived from secrets;
+ * libsecp256k1's ecmult_gen is blinded and scans its whole table.  So the path is NOT hardened against a
+ * co-tenant that observes timing or memory traffic on the same GPU.  The nonce's inversion mod n is the
+ * constant-time one.  Nor does the library control what the HIP runtime's own host-to-device staging
+ * buffer holds after a copy from pageable memory. */
+int gsv_ecdsa_sign_batch(gsv_ctx *ctx, const uint8_t *msg32, const uint8_t *seckey32, size_t n,
+                         uint8_t *sig65_out, uint8_t *status);
+int gsv_pubkey_create_batch(gsv_ctx *ctx, const uint8_t *seckey32, size_t n, uint8_t *pub65_out,
+                            uint8_t *addr20_out, uint8_t *status);
+/* Device-resident forms: every array in HBM (d_addr20_out may be NULL).  They only enqueue (one launch)
+ * on `stream` (NULL = the context stream).  No prepare call. */
+int gsv_ecdsa_sign_batch_dev(gsv_ctx *ctx, const uint8_t *d_msg32, const uint8_t *d_seckey32, size_t n,
+                             uint8_t *d_sig65_out, uint8_t *d_status, void *stream);
+int gsv_pubkey_create_batch_dev(gsv_ctx *ctx, const uint8_t *d_seckey32, size_t n, uint8_t *d_pub65_out,
+                                uint8_t *d_addr20_out, uint8_t *d_status, void *stream);
+/* Test hook of the rule on secret keys: copies bytes [off, off + n) of the context's staging arena, as
+ * they are now, to `out` (GSV_E_INVALID_ARG past the arena's end).  The host forms above stage the keys
+ * at offset 0. */
+int gsv_ctx_arena_read(gsv_ctx *ctx, size_t off, size_t n, uint8_t *out);
 
 /* ---- the ecrecover precompile (core/vm/contracts.go:78-101) ----
  * Input i = in[off[i] .. off[i+1]) = hash(32) || v(32) || r(32) || s(32), right-padded with zeros to
