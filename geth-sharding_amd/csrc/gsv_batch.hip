@@ -1,5 +1,6 @@
 // Stateless batches of the C ABI (gsv_ctx.h): Keccak-256, ecrecover and its precompile, ECDSA
-// verification and public-key parsing, crypto.Sign and public-key derivation, bn256Add / bn256ScalarMul, recoverPlain over decoded fields,
+// verification and public-key parsing, crypto.Sign and public-key derivation, ScalarMult and ECDH,
+// bn256Add / bn256ScalarMul, recoverPlain over decoded fields,
 // the synthetic signer, types.Sender over tx RLP.
 #include <thread>
 
@@ -237,6 +238,73 @@ int gsv_pubkey_create_batch(gsv_ctx* c, const uint8_t* seckey32, size_t n, uint8
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(pub65_out, d_pub, n * 65, hipMemcpyDeviceToHost, c->stream));
     if (addr20_out) HIPCHK(hipMemcpyAsync(addr20_out, d_addr, n * 20, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, c->stream));
+    return wipe.finish();
+}
+
+// ------------------------------------------------------------------ ScalarMult, ECDH (crypto/secp256k1/ext.h:104-142)
+int gsv_secp256k1_scalar_mul_batch_dev(gsv_ctx* c, const uint8_t* d_point64, const uint8_t* d_scalar32, size_t n,
+                                       uint8_t* d_point64_out, uint8_t* d_status, void* stream) {
+    if (!c || (n && (!d_point64 || !d_scalar32 || !d_point64_out || !d_status)) || n > 0xFFFFFFFFull)
+        return GSV_E_INVALID_ARG;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    KTimer t(c, GSV_K_ECRECOVER, st);
+    return hip_err(gsv::launch_ecdh(d_point64, d_scalar32, (uint32_t)n, d_point64_out, nullptr, nullptr, d_status, st));
+}
+
+int gsv_ecdh_batch_dev(gsv_ctx* c, const uint8_t* d_pub64, const uint8_t* d_seckey32, size_t n,
+                       uint8_t* d_shared32_out, uint8_t* d_keys48_out, uint8_t* d_status, void* stream) {
+    if (!c || (n && (!d_pub64 || !d_seckey32 || !d_status || (!d_shared32_out && !d_keys48_out))) ||
+        n > 0xFFFFFFFFull)
+        return GSV_E_INVALID_ARG;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    KTimer t(c, GSV_K_ECRECOVER, st);
+    return hip_err(gsv::launch_ecdh(d_pub64, d_seckey32, (uint32_t)n, nullptr, d_shared32_out, d_keys48_out, d_status,
+                                    st));
+}
+
+int gsv_secp256k1_scalar_mul_batch(gsv_ctx* c, const uint8_t* point64, const uint8_t* scalar32, size_t n,
+                                   uint8_t* point64_out, uint8_t* status) {
+    if (!c || (n && (!point64 || !scalar32 || !point64_out || !status)) || n > 0xFFFFFFFFull)
+        return GSV_E_INVALID_ARG;
+    if (n == 0) return GSV_SUCCESS;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    Layout L;
+    const ScalarMulStage p(L, n);
+    int rc = arena_reserve(c, L.n);
+    if (rc) return rc;
+    uint8_t *d_key = p.key(c->arena), *d_out = p.out(c->arena), *d_pt = p.pt(c->arena), *d_st = p.st(c->arena);
+    SecretWipe wipe{c, c->arena, p.secret};  // the scalars and the product points
+    HIPCHK(hipMemcpyAsync(d_key, scalar32, n * 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_pt, point64, n * 64, hipMemcpyHostToDevice, c->stream));
+    rc = gsv_secp256k1_scalar_mul_batch_dev(c, d_pt, d_key, n, d_out, d_st, c->stream);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(point64_out, d_out, n * 64, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, c->stream));
+    return wipe.finish();
+}
+
+int gsv_ecdh_batch(gsv_ctx* c, const uint8_t* pub64, const uint8_t* seckey32, size_t n, uint8_t* shared32_out,
+                   uint8_t* keys48_out, uint8_t* status) {
+    if (!c || (n && (!pub64 || !seckey32 || !status || (!shared32_out && !keys48_out))) || n > 0xFFFFFFFFull)
+        return GSV_E_INVALID_ARG;
+    if (n == 0) return GSV_SUCCESS;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    Layout L;
+    const EcdhStage p(L, n, shared32_out != nullptr, keys48_out != nullptr);
+    int rc = arena_reserve(c, L.n);
+    if (rc) return rc;
+    uint8_t *d_key = p.key(c->arena), *d_pt = p.pt(c->arena), *d_st = p.st(c->arena);
+    uint8_t *d_sh = p.shared(c->arena), *d_keys = p.keys(c->arena);  // nullptr when not asked for
+    SecretWipe wipe{c, c->arena, p.secret};  // the secret keys, the shared secrets, the derived keys
+    HIPCHK(hipMemcpyAsync(d_key, seckey32, n * 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_pt, pub64, n * 64, hipMemcpyHostToDevice, c->stream));
+    rc = gsv_ecdh_batch_dev(c, d_pt, d_key, n, d_sh, d_keys, d_st, c->stream);
+    if (rc) return rc;
+    if (shared32_out) HIPCHK(hipMemcpyAsync(shared32_out, d_sh, n * 32, hipMemcpyDeviceToHost, c->stream));
+    if (keys48_out) HIPCHK(hipMemcpyAsync(keys48_out, d_keys, n * 48, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, c->stream));
     return wipe.finish();
 }

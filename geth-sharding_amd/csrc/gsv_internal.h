@@ -31,6 +31,12 @@ hipError_t launch_ecsign(const uint8_t* msg32, const uint8_t* seckey32, uint32_t
 hipError_t launch_pubkey_create(const uint8_t* seckey32, uint32_t n, const uint4* gtab, uint8_t* pub65,
                                 uint8_t* addr20, uint8_t* status, hipStream_t st);
 
+// ecdh.hip: secp256k1_ext_scalar_mul and what ECIES derives from its X.  Outputs that are null are not
+// written: xy64 (X || Y), x32 (X), keys48 (Ke || Km); status GSV_ST_OK / GSV_ST_INVALID_KEY /
+// GSV_ST_INVALID_CURVE
+hipError_t launch_ecdh(const uint8_t* point64, const uint8_t* scalar32, uint32_t n, uint8_t* xy64, uint8_t* x32,
+                       uint8_t* keys48, uint8_t* status, hipStream_t st);
+
 // keccak.hip
 hipError_t launch_keccak256(const uint8_t* data, const uint64_t* off, uint32_t n, uint8_t* out32,
                             hipStream_t st);

@@ -74,6 +74,25 @@ struct PubkeyCreateStage {
     PubkeyCreateStage(Layout& L, size_t n, bool want_addr)
         : key(L.buf(n * 32)), pub(L.buf(n * 65)), addr(L.buf(n * 20, want_addr)), st(L.buf(n)) {}
 };
+// gsv_secp256k1_scalar_mul_batch, gsv_ecdh_batch.  Every secret region comes FIRST and contiguous: the
+// scalars, then the secret outputs (the product point; the shared X and the derived keys, each only
+// when asked for).  `secret` is the end of the last of them: the host form overwrites [0, secret) of
+// the stage before it returns, whatever else is staged behind (the public points, the status bytes).
+struct ScalarMulStage {
+    B8 key, out;
+    size_t secret;
+    B8 pt, st;
+    ScalarMulStage(Layout& L, size_t n)
+        : key(L.buf(n * 32)), out(L.buf(n * 64)), secret(L.n), pt(L.buf(n * 64)), st(L.buf(n)) {}
+};
+struct EcdhStage {
+    B8 key, shared, keys;
+    size_t secret;
+    B8 pt, st;
+    EcdhStage(Layout& L, size_t n, bool want_shared, bool want_keys)
+        : key(L.buf(n * 32)), shared(L.buf(n * 32, want_shared)), keys(L.buf(n * 48, want_keys)), secret(L.n),
+          pt(L.buf(n * 64)), st(L.buf(n)) {}
+};
 // fixed-size records in, fixed-size results and a status byte out: gsv_ecrecover_precompile_batch
 // (128 -> 32), bn_g1_host (128 or 96 -> 64)
 struct RecordStage {

@@ -780,6 +780,68 @@ def _pubkey_create_batch_dev(self, key_t, pub_t, addr_t, st_t, stream=None):
                                                   _tptr(addr_t) if addr_t is not None else None, _tptr(st_t), sp))
 
 
+def _point_rows(points):
+    points = np.ascontiguousarray(points, np.uint8)
+    if points.size % 64:
+        raise ValueError("points are 64 bytes each (X || Y)")
+    return points.reshape(-1, 64)
+
+
+def _secp256k1_scalar_mul_batch(self, points, scalars):
+    """BitCurve.ScalarMult over a batch (gsv.h gsv_secp256k1_scalar_mul_batch): points (n,64) uint8 X || Y,
+    scalars (n,32) uint8 big-endian.  Returns (out (n,64) X || Y of k P, status (n,)): ST_INVALID_KEY for a
+    scalar of 0 or >= n, ST_INVALID_CURVE for a point off the curve, a zero row for both.  The device copies
+    of the scalars and the products are overwritten before the call returns."""
+    points = _point_rows(points)
+    scalars = _seckey_rows(scalars)
+    n = points.shape[0]
+    if scalars.shape[0] != n:
+        raise ValueError("points and scalars batch sizes differ")
+    out = np.zeros((n, 64), np.uint8)
+    st = np.zeros(n, np.uint8)
+    if n:
+        check(_lib.load().gsv_secp256k1_scalar_mul_batch(self._h, _ptr(points), _ptr(scalars), n, _ptr(out), _ptr(st)))
+    return out, st
+
+
+def _ecdh_batch(self, pubs, keys, want_shared=True, want_keys=False):
+    """ECDH over a batch (gsv.h gsv_ecdh_batch): pubs (n,64) uint8 public points X || Y, keys (n,32) uint8
+    big-endian secret keys.  Returns (shared (n,32) or None, keys48 (n,48) Ke || Km or None, status (n,));
+    the statuses and the zero rows are scalar_mul_batch's."""
+    if not (want_shared or want_keys):
+        raise ValueError("ask for the shared secrets, the derived keys or both")
+    pubs = _point_rows(pubs)
+    keys = _seckey_rows(keys)
+    n = pubs.shape[0]
+    if keys.shape[0] != n:
+        raise ValueError("pubs and keys batch sizes differ")
+    shared = np.zeros((n, 32), np.uint8) if want_shared else None
+    k48 = np.zeros((n, 48), np.uint8) if want_keys else None
+    st = np.zeros(n, np.uint8)
+    if n:
+        check(_lib.load().gsv_ecdh_batch(self._h, _ptr(pubs), _ptr(keys), n, _ptr(shared) if want_shared else None,
+                                         _ptr(k48) if want_keys else None, _ptr(st)))
+    return shared, k48, st
+
+
+def _secp256k1_scalar_mul_batch_dev(self, pt_t, k_t, out_t, st_t, stream=None):
+    """torch uint8 CUDA tensors: pt_t (n,64), k_t (n,32) scalars, out_t (n,64), st_t (n,); only enqueues on
+    `stream`.  k_t and out_t are the caller's to wipe."""
+    n = pt_t.shape[0]
+    sp = _sp(stream)
+    check(_lib.load().gsv_secp256k1_scalar_mul_batch_dev(self._h, _tptr(pt_t), _tptr(k_t), n, _tptr(out_t),
+                                                         _tptr(st_t), sp))
+
+
+def _ecdh_batch_dev(self, pub_t, key_t, shared_t, keys_t, st_t, stream=None):
+    """torch uint8 CUDA tensors: pub_t (n,64), key_t (n,32) secret keys, shared_t (n,32) or None, keys_t
+    (n,48) or None (not both None), st_t (n,); only enqueues on `stream`."""
+    n = pub_t.shape[0]
+    sp = _sp(stream)
+    check(_lib.load().gsv_ecdh_batch_dev(self._h, _tptr(pub_t), _tptr(key_t), n, _tptr(shared_t), _tptr(keys_t),
+                                         _tptr(st_t), sp))
+
+
 def _arena_read(self, off, n):
     """Test hook (gsv.h gsv_ctx_arena_read): n bytes of the staging arena from `off`, as they are now."""
     out = np.zeros(n, np.uint8)
@@ -804,6 +866,10 @@ Context.ecdsa_sign_batch = _ecdsa_sign_batch
 Context.ecdsa_sign_batch_dev = _ecdsa_sign_batch_dev
 Context.pubkey_create_batch = _pubkey_create_batch
 Context.pubkey_create_batch_dev = _pubkey_create_batch_dev
+Context.secp256k1_scalar_mul_batch = _secp256k1_scalar_mul_batch
+Context.secp256k1_scalar_mul_batch_dev = _secp256k1_scalar_mul_batch_dev
+Context.ecdh_batch = _ecdh_batch
+Context.ecdh_batch_dev = _ecdh_batch_dev
 Context._arena_read = _arena_read
 Context.prepared_shapes = _prepared_shapes
 Context.bn256_add_batch = _bn256_add_batch

@@ -26,6 +26,25 @@ ST_BAD_RLP = 8
 ST_BN_BAD_INPUT = 9
 ST_PROPOSER_MISMATCH = 10
 ST_INVALID_KEY = 11
+ST_INVALID_CURVE = 12
+
+# a short text per per-item status: the reference's error string where it has one (include/gsv.h names
+# the sources)
+STATUS_STRINGS = {
+    ST_OK: "ok",
+    ST_INVALID_MSG_LEN: "invalid message length, need 32 bytes",
+    ST_INVALID_SIG_LEN: "invalid signature length",
+    ST_INVALID_RECID: "invalid signature recovery id",
+    ST_RECOVER_FAILED: "recovery failed",
+    ST_INVALID_SIG: "invalid transaction v, r, s values",
+    ST_INVALID_CHAIN_ID: "invalid chain id for signer",
+    ST_INVALID_PUBKEY: "invalid public key",
+    ST_BAD_RLP: "rlp: transaction does not decode",
+    ST_BN_BAD_INPUT: "bn256: malformed point",
+    ST_PROPOSER_MISMATCH: "recovered signer is not the header's proposer",
+    ST_INVALID_KEY: "invalid private key",
+    ST_INVALID_CURVE: "ecies: invalid elliptic curve",
+}
 
 SIGNER_EIP155 = 0
 SIGNER_HOMESTEAD = 1
@@ -88,6 +107,10 @@ SIGNATURES = [
     ("gsv_ecdsa_sign_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     ("gsv_pubkey_create_batch", ctypes.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
     ("gsv_pubkey_create_batch_dev", ctypes.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    ("gsv_secp256k1_scalar_mul_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    ("gsv_secp256k1_scalar_mul_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    ("gsv_ecdh_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    ("gsv_ecdh_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("gsv_ctx_arena_read", ctypes.c_int, [_vp, _sz, _sz, _vp]),
     ("gsv_sender_batch", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_int, _vp, _vp]),
     ("gsv_tx_sender_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, ctypes.c_int, _vp, _vp]),

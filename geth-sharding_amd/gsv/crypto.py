@@ -14,6 +14,9 @@
     Sign(hash, prv)             crypto/signature_cgo.go:54-61 -> secp256k1.Sign (secp256.go:70-99)
     SignBatch(hashes, keys)     batch form: per-item status codes
     PubkeyFromSeckey(prv)       secp256k1_ec_pubkey_create, the derivation behind crypto.ToECDSA
+    ScalarMult(x, y, k)         crypto/secp256k1/curve.go:221-254 -> secp256k1_ext_scalar_mul
+    ScalarBaseMult(k)           crypto/secp256k1/curve.go:257-259
+    ScalarMultBatch(...)        batch form: per-item status codes
 
 Errors mirror crypto/secp256k1/secp256.go:54-62 and are raised as exceptions.
 """
@@ -183,6 +186,42 @@ def PubkeyFromSeckey(prv, ctx=None) -> bytes:
     if st[0] != _lib.ST_OK:
         raise ErrInvalidKey("invalid private key")
     return bytes(pub[0])
+
+
+# the generator (crypto/secp256k1/curve.go:293-294 theCurve.Gx, Gy)
+S256_GX = 0x79BE667EF9DCBBAC55A06295CE870B07029BFCDB2DCE28D959F2815B16F81798
+S256_GY = 0x483ADA7726A3C4655DA4FBFC0E1108A8FD17B448A68554199C47D08FFB10D4B8
+
+
+def ScalarMultBatch(points, scalars, ctx=None):
+    """Batch BitCurve.ScalarMult: points (n,64) uint8 X || Y, scalars (n,32) uint8 big-endian.  Returns
+    (out (n,64) X || Y of k P, status (n,)): ST_INVALID_KEY and a zero row for a scalar of 0 or >= n (where
+    the reference returns (nil, nil)), ST_INVALID_CURVE and a zero row for a point off the curve (where
+    the reference computes on another curve: include/gsv.h)."""
+    return (ctx or default_context()).secp256k1_scalar_mul_batch(points, scalars)
+
+
+def ScalarMult(x: int, y: int, k: bytes, ctx=None):
+    """crypto/secp256k1/curve.go:221-254 BitCurve.ScalarMult: (x, y) of k (x, y), k big-endian bytes,
+    left-padded to 32; more than 32 bytes raise ValueError (the reference panics).  (None, None) where the
+    reference returns (nil, nil), a scalar of 0 or >= n, and for a point off the curve (the reference's
+    result there is an artefact).  Coordinates are non-negative 256-bit values (math.ReadBits would keep
+    the low 256 bits of a larger one; here that is a ValueError)."""
+    k = bytes(k)
+    if len(k) > 32:
+        raise ValueError("can't handle scalars > 256 bits")
+    if x < 0 or y < 0 or x >> 256 or y >> 256:
+        raise ValueError("coordinates are 256-bit values")
+    pt = np.frombuffer(x.to_bytes(32, "big") + y.to_bytes(32, "big"), np.uint8)[None]
+    out, st = ScalarMultBatch(pt, np.frombuffer(k.rjust(32, b"\0"), np.uint8)[None], ctx)
+    if st[0] != _lib.ST_OK:
+        return None, None
+    return int.from_bytes(bytes(out[0, :32]), "big"), int.from_bytes(bytes(out[0, 32:]), "big")
+
+
+def ScalarBaseMult(k: bytes, ctx=None):
+    """crypto/secp256k1/curve.go:257-259: ScalarMult on the generator."""
+    return ScalarMult(S256_GX, S256_GY, k, ctx)
 
 
 def PubkeyToAddress(pub65: bytes) -> bytes:

@@ -20,6 +20,11 @@
  *                                 (crypto/signature_cgo.go:54-61)
  *   gsv_pubkey_create_batch    <- secp256k1_ec_pubkey_create (libsecp256k1/src/secp256k1.c), the key
  *                                 derivation behind crypto.ToECDSA / crypto.PubkeyToAddress
+ *   gsv_secp256k1_scalar_mul_batch <- secp256k1_ext_scalar_mul (crypto/secp256k1/ext.h:104-142) via
+ *                                 BitCurve.ScalarMult / ScalarBaseMult (crypto/secp256k1/curve.go:221-259)
+ *   gsv_ecdh_batch             <- ecies.PrivateKey.GenerateShared (crypto/ecies/ecies.go:121-138) and the
+ *                                 key derivation of ecies.Encrypt / Decrypt (ecies.go:264-277, 347-356);
+ *                                 the RLPx handshake's two GenerateShared calls (p2p/rlpx.go:243, 276)
  *   gsv_sender_batch           <- recoverPlain (core/types/transaction_signing.go:222-247)
  *                                 + crypto.ValidateSignatureValues (crypto/crypto.go:181-192)
  *   gsv_tx_sender_batch        <- types.Sender(signer, tx) (core/types/transaction_signing.go:72-89,
@@ -101,6 +106,7 @@ extern "C" {
 #define GSV_ST_BN_BAD_INPUT 9      /* bn256 unmarshal / curve / subgroup failure */
 #define GSV_ST_PROPOSER_MISMATCH 10 /* recovered signer != header ProposerAddress */
 #define GSV_ST_INVALID_KEY 11      /* secp256k1.ErrInvalidKey          secp256.go:58 */
+#define GSV_ST_INVALID_CURVE 12    /* ecies.ErrInvalidCurve            ecies/ecies.go:47 */
 
 /* signer kinds for gsv_tx_sender_batch (core/types/transaction_signing.go) */
 #define GSV_SIGNER_EIP155 0
@@ -258,9 +264,53 @@ int gsv_ecdsa_sign_batch_dev(gsv_ctx *ctx, const uint8_t *d_msg32, const uint8_t
                              uint8_t *d_sig65_out, uint8_t *d_status, void *stream);
 int gsv_pubkey_create_batch_dev(gsv_ctx *ctx, const uint8_t *d_seckey32, size_t n, uint8_t *d_pub65_out,
                                 uint8_t *d_addr20_out, uint8_t *d_status, void *stream);
+/* ---- ScalarMult and ECDH shared secrets ----
+ * secp256k1_ext_scalar_mul (crypto/secp256k1/ext.h:104-142) behind BitCurve.ScalarMult (curve.go:221-259):
+ * point64 = n x 64 B points X || Y (big-endian), scalar32 = n x 32 B big-endian scalars k.
+ *   - A scalar of 0 or >= n gets status GSV_ST_INVALID_KEY and a zero row: the reference returns 0 and
+ *     leaves its buffer alone, which Go turns into (nil, nil) and ecies.GenerateShared into
+ *     ErrSharedKeyIsPointAtInfinity.  This rule is tested first: it is the reference's only failure.
+ *   - A coordinate >= p is accepted and reduced mod p (fe_set_b32's verdict is ignored in ext.h).
+ *   - Else status GSV_ST_OK and point64_out[i] = X || Y of the affine k P, byte for byte the reference's.
+ *   - THE ONE DIVERGENCE.  A point with Y^2 != X^3 + 7 (after the reduction) and a scalar in range gets
+ *     status GSV_ST_INVALID_CURVE and a zero row.  The reference returns 1 and the output of its addition
+ *     formulas on another curve y^2 = x^3 + b'; orders there are not n, ecmult_const assumes no
+ *     exceptional case, and the ladder here is only correct for a point of order n, so that value is an
+ *     artefact nobody should consume: ecies.Decrypt checks IsOnCurve before it multiplies (ecies.go:337),
+ *     as p2p/discover and discv5 do on the keys they parse.  The status mirrors ecies.ErrInvalidCurve.
+ * gsv_ecdh_batch is the same multiplication of public point pub64[i] by secret key seckey32[i], under the
+ * same three statuses, and returns what ECIES makes of its X:
+ *   shared32_out (may be NULL): X, 32 bytes, left-padded with zeros: GenerateShared(pub, 16, 16);
+ *   keys48_out (may be NULL): Ke || Km of ECIES_AES128_SHA256 (crypto/ecies/params.go:69-76) with s1
+ *     empty, as ecies.Encrypt(rand, pub, m, nil, nil) and RLPx derive them: K = SHA256(00 00 00 01 || X)
+ *     (concatKDF, ecies.go:167-192), Ke = K[0:16], Km = SHA256(K[16:32]) (ecies.go:273-277).
+ * At least one of the two is asked for (both NULL with n > 0: GSV_E_INVALID_ARG).  Every output row of
+ * a failed item is zero bytes.
+ *
+ * Secrets: the scalar, the product point ("usually secret", ext.h:109), the shared X and the derived
+ * keys.  The host forms stage all of them FIRST in the context's device arena, contiguous from offset 0,
+ * and overwrite that whole region on the context stream, before their final synchronisation, on every
+ * return that follows the copy-in (error returns included); the public points and the status bytes
+ * behind it are left.  The _dev forms write secrets only to the caller's output buffers.
+ * What this path does NOT promise, beyond the caveat of the Sign block above: the GLV ladder's table of
+ * odd multiples (LDS and a private array) is indexed by 4-bit digits of the secret scalar, and the
+ * ladder's exceptional-case guards are wave-uniform tests on values derived from secrets, so a rare
+ * case in one lane costs its whole wave time.  libsecp256k1's ecmult_const is constant-time.  This
+ * path is NOT hardened against a co-tenant that observes timing or memory traffic on the same GPU.  The
+ * inversion of Z mod p is the constant-time one, and no lane leaves the schedule early. */
+int gsv_secp256k1_scalar_mul_batch(gsv_ctx *ctx, const uint8_t *point64, const uint8_t *scalar32, size_t n,
+                                   uint8_t *point64_out, uint8_t *status);
+int gsv_ecdh_batch(gsv_ctx *ctx, const uint8_t *pub64, const uint8_t *seckey32, size_t n,
+                   uint8_t *shared32_out, uint8_t *keys48_out, uint8_t *status);
+/* Device-resident forms: every array in HBM (one of d_shared32_out, d_keys48_out may be NULL).  They only
+ * enqueue (one launch) on `stream` (NULL = the context stream).  No prepare call. */
+int gsv_secp256k1_scalar_mul_batch_dev(gsv_ctx *ctx, const uint8_t *d_point64, const uint8_t *d_scalar32,
+                                       size_t n, uint8_t *d_point64_out, uint8_t *d_status, void *stream);
+int gsv_ecdh_batch_dev(gsv_ctx *ctx, const uint8_t *d_pub64, const uint8_t *d_seckey32, size_t n,
+                       uint8_t *d_shared32_out, uint8_t *d_keys48_out, uint8_t *d_status, void *stream);
 /* Test hook of the rule on secret keys: copies bytes [off, off + n) of the context's staging arena, as
- * they are now, to `out` (GSV_E_INVALID_ARG past the arena's end).  The host forms above stage the keys
- * at offset 0. */
+ * they are now, to `out` (GSV_E_INVALID_ARG past the arena's end).  The host forms above stage their
+ * secrets from offset 0. */
 int gsv_ctx_arena_read(gsv_ctx *ctx, size_t off, size_t n, uint8_t *out);
 
 /* ---- the ecrecover precompile (core/vm/contracts.go:78-101) ----

@@ -1,5 +1,5 @@
 """Operation counts of OUR kernels per unit of work, from the instrumented build
-(geth-sharding_amd/csrc/opcount.cuh; built by `VSRCS="ecrecover bn256 bn_g1 notary collation"
+(geth-sharding_amd/csrc/opcount.cuh; built by `VSRCS="ecrecover ecverify ecdh bn256 bn_g1 notary collation"
 tools/build_variant.sh opcount -DGSV_OPCOUNT`), at the bench's batch sizes:
 
     recovery       one k_ecrecover lane of the configs[1] batch (2^20 signatures)
@@ -10,6 +10,10 @@ tools/build_variant.sh opcount -DGSV_OPCOUNT`), at the bench's batch sizes:
     bn256_scalar_mul / bn256_scalar_mul_bitserial / bn256_add
                    one item of a 65,536-item batch of the G1 precompiles (k_bn_g1_mul in its GLV and
                    bit-serial forms, k_bn_g1_add): points s_i G, scalars uniform over 256 bits
+    secp256k1_scalar_mul / ecdh_x / ecdh_keys / ecdsa_verify_uncompressed
+                   one item of a 65,536-item batch of k_ecdh in its three output modes and, on the same
+                   keys, of k_ecverify; `python tools/count_ops.py ecdh` prints these four alone (then
+                   VSRCS="ecverify ecdh" is enough)
 
 "mad" is the number of v_mad_u64_u32 (32 x 32 -> 64-bit multiply-adds: the unit of the VALU MAC
 roofline) our kernels execute, from the op counts and each op's mad count in our limb layout:
@@ -53,12 +57,52 @@ def per_unit(c, n):
     return {k: round(v / n, 3) for k, v in c.items() if v}
 
 
+W = {"fe_mul": 108, "fe_sqr": 72, "sc_mul": 64, "sc_sqr": 36, "bn_mul": 81, "bn_redc": 81, "fe_dot": 189, "fe_dot_ms": 153}
+
+
+def ecdh_counts(ctx, dev):
+    """k_ecdh's three output modes and, from the same inputs, k_ecverify on 65-byte keys: one item of a
+    65,536-item batch (points = the synthetic signer's keys, scalars = its message hashes)"""
+    n = 65536
+    msg = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+    sig = torch.empty((n, 65), dtype=torch.uint8, device=dev)
+    pub = torch.empty((n, 65), dtype=torch.uint8, device=dev)
+    ctx.synth_sign_dev(3000, msg, sig, pub)
+    pts = pub[:, 1:].contiguous()
+    sig64 = sig[:, :64].contiguous()
+    len65 = torch.full((n,), 65, dtype=torch.uint8, device=dev)
+    xy = torch.empty((n, 64), dtype=torch.uint8, device=dev)
+    x = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+    keys = torch.empty((n, 48), dtype=torch.uint8, device=dev)
+    st = torch.empty((n,), dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
+    read("ecdh")
+    read("ecverify")
+    res = {}
+    for name, fn in (("secp256k1_scalar_mul", lambda: ctx.secp256k1_scalar_mul_batch_dev(pts, msg, xy, st)),
+                     ("ecdh_x", lambda: ctx.ecdh_batch_dev(pts, msg, x, None, st)),
+                     ("ecdh_keys", lambda: ctx.ecdh_batch_dev(pts, msg, None, keys, st)),
+                     ("ecdsa_verify_uncompressed", lambda: ctx.ecdsa_verify_batch_dev(msg, sig64, pub, len65, st))):
+        fn()
+        torch.cuda.synchronize()
+        verify = name == "ecdsa_verify_uncompressed"
+        assert int(st.min()) == 1 if verify else int(st.max()) == 0
+        c = per_unit(read("ecverify" if verify else "ecdh"), n)
+        c["mac_equiv"] = round(sum(W[k] * c.get(k, 0) for k in ("fe_mul", "fe_sqr", "sc_mul", "sc_sqr", "fe_dot", "fe_dot_ms")), 1)
+        res[name] = c
+    return res
+
+
 def main():
     ctx = gsv.Context(0)
     dev = torch.device("cuda", 0)
-    W = {"fe_mul": 108, "fe_sqr": 72, "sc_mul": 64, "sc_sqr": 36, "bn_mul": 81, "bn_redc": 81, "fe_dot": 189, "fe_dot_ms": 153}
     out = {"build": "variants/opcount (-DGSV_OPCOUNT)", "unit": "v_mad_u64_u32 per unit of work",
            "weights_mad_per_op": W}
+    if sys.argv[1:] == ["ecdh"]:  # the ScalarMult / ECDH kernel alone, beside verification
+        out.update(ecdh_counts(ctx, dev))
+        json.dump(out, sys.stdout, indent=1)
+        print()
+        return
     # ---- configs[1]: 2^20 recoveries
     n = 1 << 20
     msg = torch.empty((n, 32), dtype=torch.uint8, device=dev)
@@ -141,6 +185,7 @@ def main():
     c = per_unit(read("bn_g1"), n)
     c["mac_equiv"] = round(W["bn_mul"] * c.get("bn_mul", 0) + W["bn_redc"] * c.get("bn_redc", 0), 1)
     out["bn256_add"] = c
+    out.update(ecdh_counts(ctx, dev))
     json.dump(out, sys.stdout, indent=1)
     print()
 
