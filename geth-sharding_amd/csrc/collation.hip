@@ -184,6 +184,16 @@ hipError_t launch_header_verify(const uint8_t* d_sid32, const uint8_t* d_root32,
     return hipGetLastError();
 }
 
+// the unsigned hash alone (k_header_hash never reads sig65 for it)
+hipError_t launch_header_hash_unsigned(const uint8_t* d_sid32, const uint8_t* d_root32, const uint8_t* d_per32,
+                                       const uint8_t* d_prop20, uint32_t n, uint8_t* d_hash32, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    dim3 g((n + HDR_LANES - 1) / HDR_LANES);
+    hipLaunchKernelGGL(k_header_hash, g, dim3(HDR_LANES), 0, st, d_sid32, d_root32, d_per32, d_prop20,
+                       (const uint8_t*)nullptr, (const uint8_t*)nullptr, n, d_hash32, (uint8_t*)nullptr);
+    return hipGetLastError();
+}
+
 }  // namespace gsv
 
 GSV_OPCOUNT_READER(collation)

@@ -180,25 +180,6 @@ int gsv_pubkey_create_batch_dev(gsv_ctx* c, const uint8_t* d_seckey32, size_t n,
                                              st));
 }
 
-// The staged secret keys of a host form: overwritten on the context stream, and the stream waited
-// for, on every way out of the scope that follows the copy-in (HIPCHK's early returns included).
-// finish() is the success path's last step and reports the two calls' outcome.
-struct SecretWipe {
-    gsv_ctx* c;
-    uint8_t* p;
-    size_t bytes;
-    bool done = false;
-    int finish() {
-        done = true;
-        hipError_t a = hipMemsetAsync(p, 0, bytes, c->stream);
-        hipError_t b = hipStreamSynchronize(c->stream);
-        return hip_err(a != hipSuccess ? a : b);
-    }
-    ~SecretWipe() {
-        if (!done) finish();
-    }
-};
-
 int gsv_ecdsa_sign_batch(gsv_ctx* c, const uint8_t* msg32, const uint8_t* seckey32, size_t n, uint8_t* sig65_out,
                          uint8_t* status) {
     if (!c || (n && (!msg32 || !seckey32 || !sig65_out || !status)) || n > 0xFFFFFFFFull) return GSV_E_INVALID_ARG;

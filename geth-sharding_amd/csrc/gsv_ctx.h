@@ -4,6 +4,7 @@
 //   gsv_trie.hip     chunk root, DeriveSha, Proof of Custody, collation headers
 //   gsv_pairing.hip  BN254 pairing check
 //   gsv_notary.hip   notary validation, shard partition + RCCL all-gather
+//   gsv_proposer.hip blob codec (Serialize / Deserialize), createCollation
 //
 // Host-pointer entry points stage through a grow-only device arena on the context's stream and are
 // synchronous.  *_dev entry points take HBM-resident buffers and the caller's stream and only
@@ -37,7 +38,8 @@ namespace gsv {
 namespace api {
 
 enum ShapeKind : uint64_t {
-    SK_CHUNK = 1, SK_PAIRING = 2, SK_NOTARY = 3, SK_DERIVE = 4, SK_POC = 5, SK_HEADER = 6, SK_PARTITION = 7
+    SK_CHUNK = 1, SK_PAIRING = 2, SK_NOTARY = 3, SK_DERIVE = 4, SK_POC = 5, SK_HEADER = 6, SK_PARTITION = 7,
+    SK_BLOB_SER = 8, SK_BLOB_DESER = 9, SK_PROPOSER = 10
 };
 
 // scatter run: roots of group positions [from, from + count) go to output indices [dst, dst + count)
@@ -119,6 +121,15 @@ struct Shape {
         int ranks = 1, rank = 0;
         size_t o_lroot = 0, o_lntx = 0, o_lbm = 0, o_block = 0, o_all = 0;
     } part;
+    struct BlobSer {  // SK_BLOB_SER, SK_PROPOSER: the serialize plan (gsv_proposer.hip)
+        size_t o_ents = 0, o_cidx = 0, o_over = 0;
+        uint64_t nchunks = 0, begin = 0, end = 0, first_blob = 0;
+        bool any_over = false;
+    } ser;
+    struct BlobDeser {  // SK_BLOB_DESER
+        size_t o_off = 0, o_len = 0, o_doff = 0, o_recs = 0;
+        uint64_t begin = 0, end = 0, max_region = 0;
+    } deser;
 
     Shape() = default;
     Shape(const Shape&) = delete;
@@ -218,6 +229,25 @@ inline int hip_err(hipError_t e) { return e == hipSuccess ? GSV_SUCCESS : GSV_E_
         hipError_t _e = (x);                       \
         if (_e != hipSuccess) return GSV_E_HIP;    \
     } while (0)
+
+// The staged secret keys of a host form: overwritten on the context stream, and the stream waited
+// for, on every way out of the scope that follows the copy-in (HIPCHK's early returns included).
+// finish() is the success path's last step and reports the two calls' outcome.
+struct SecretWipe {
+    gsv_ctx* c;
+    uint8_t* p;
+    size_t bytes;
+    bool done = false;
+    int finish() {
+        done = true;
+        hipError_t a = hipMemsetAsync(p, 0, bytes, c->stream);
+        hipError_t b = hipStreamSynchronize(c->stream);
+        return hip_err(a != hipSuccess ? a : b);
+    }
+    ~SecretWipe() {
+        if (!done) finish();
+    }
+};
 
 inline bool capturing(hipStream_t st) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;

@@ -102,7 +102,31 @@ hipError_t launch_bn256_g1_add(const uint8_t* d_in128, uint32_t n, uint8_t* d_ou
 hipError_t launch_bn256_g1_mul(const uint8_t* d_in96, uint32_t n, uint8_t* d_out64, uint8_t* d_status,
                                int bitserial, hipStream_t st);
 
+// collation.hip: CollationHeader.Hash() with ProposerSignature empty (k_header_hash alone: the hash the
+// proposer signs), no nil fields
+hipError_t launch_header_hash_unsigned(const uint8_t* d_sid32, const uint8_t* d_root32, const uint8_t* d_per32,
+                                       const uint8_t* d_prop20, uint32_t n, uint8_t* d_hash32, hipStream_t st);
+
+// blob.hip: the blob codec (blob_codec.h) and the proposer's mask.  d_ents: blobc::BlobEnt per blob;
+// d_chunk_blob: the blob of each output chunk; output and data regions 16-byte aligned
+hipError_t launch_blob_serialize(const uint8_t* d_blobs, uint64_t begin, uint64_t end, const void* d_ents,
+                                 const uint32_t* d_chunk_blob, const uint8_t* d_skip_evm, uint64_t nchunks,
+                                 uint8_t* d_out, hipStream_t st);
+hipError_t launch_blob_strip(const uint8_t* d_bodies, uint64_t begin, uint64_t end, const uint64_t* d_body_off,
+                             const uint32_t* d_body_len, const uint64_t* d_data_off, uint32_t n, uint64_t max_region,
+                             uint8_t* d_data, hipStream_t st);
+hipError_t launch_blob_unpack(const void* d_recs, const uint32_t* d_cnt, uint32_t n, uint32_t max_blobs,
+                              uint32_t* d_start, uint32_t* d_len, uint8_t* d_skip, hipStream_t st);
+hipError_t launch_proposer_mask(const uint8_t* d_over, uint32_t n, uint8_t* d_root32, uint8_t* d_hash32,
+                                uint8_t* d_sig65, uint8_t* d_status, hipStream_t st);
+
 // notary.hip
+struct BlobRec {  // k_blob_index's record of one blob
+    uint32_t first_chunk;  // chunk index in the shard body
+    uint32_t nchunks;
+    uint32_t len;          // data bytes = 31 * (nchunks - 1) + terminal length
+    uint32_t skip_evm;
+};
 size_t blob_rec_bytes();
 hipError_t launch_partition_pack(const uint8_t* d_root, const uint32_t* d_ntx, const uint8_t* d_bm, uint32_t n,
                                  uint32_t per, uint32_t R, uint32_t bm, int32_t status, uint8_t* d_block,

@@ -24,13 +24,6 @@
 
 namespace gsv {
 
-struct BlobRec {
-    uint32_t first_chunk;  // chunk index in the shard body
-    uint32_t nchunks;
-    uint32_t len;          // data bytes = 31 * (nchunks - 1) + terminal length
-    uint32_t skip_evm;
-};
-
 // ---------------------------------------------------------------- blob index (marshal.go:144-198)
 constexpr int BI_THREADS = 1024;
 constexpr uint32_t BI_MAX_CHUNKS = (1u << 20) / 32;  // bodies are <= 2^20 bytes (notary_shape refuses more)

@@ -171,6 +171,27 @@ struct PartitionStage {
           ontx(L.buf<uint32_t>(n_total * 4)), obm(L.buf(n_total * d.bm)), rst(L.buf<int32_t>((size_t)N * 4)),
           gathered(L.n), own(L, bytes, d.n, max_txs, want_senders, want_status) {}
 };
+struct BlobSerStage {  // gsv_blob_serialize_batch
+    B8 blobs, skip, bodies;
+    BlobSerStage(Layout& L, size_t blob_bytes, size_t nblobs, bool has_skip, size_t body_bytes)
+        : blobs(L.buf(blob_bytes)), skip(L.buf(nblobs, has_skip)), bodies(L.buf(body_bytes)) {}
+};
+struct BlobDeserStage {  // gsv_blob_deserialize_batch
+    B8 bodies;
+    Buf<uint32_t> nblobs, start, len;
+    B8 skip, data;
+    BlobDeserStage(Layout& L, size_t body_bytes, size_t n, uint32_t max_blobs, size_t data_bytes)
+        : bodies(L.buf(body_bytes)), nblobs(L.buf<uint32_t>(n * 4)), start(L.buf<uint32_t>(n * max_blobs * 4)),
+          len(L.buf<uint32_t>(n * max_blobs * 4)), skip(L.buf(n * max_blobs)), data(L.buf(data_bytes)) {}
+};
+// gsv_proposer_create_collations.  The secret keys come FIRST, as in SignStage: the region the host
+// form overwrites before it returns is [key.off, key.off + key.bytes).
+struct ProposerStage {
+    B8 key, blobs, sid, per, prop, bodies, root, hash, sig, st;
+    ProposerStage(Layout& L, size_t n, size_t blob_bytes, size_t body_bytes)
+        : key(L.buf(n * 32)), blobs(L.buf(blob_bytes)), sid(L.buf(n * 32)), per(L.buf(n * 32)), prop(L.buf(n * 20)),
+          bodies(L.buf(body_bytes)), root(L.buf(n * 32)), hash(L.buf(n * 32)), sig(L.buf(n * 65)), st(L.buf(n)) {}
+};
 struct HeaderStage {  // gsv_collation_header_verify_batch
     B8 sid, root, per, prop, sig, nil, hash, signer, st, scr;
     HeaderStage(Layout& L, size_t n, size_t scratch_bytes, bool has_nil, bool want_hash, bool want_signer)

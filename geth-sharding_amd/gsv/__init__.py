@@ -876,3 +876,178 @@ Context.bn256_add_batch = _bn256_add_batch
 Context.bn256_scalar_mul_batch = _bn256_scalar_mul_batch
 Context.bn256_add_batch_dev = _bn256_add_batch_dev
 Context.bn256_scalar_mul_batch_dev = _bn256_scalar_mul_batch_dev
+
+
+# ------------------------------------------------------------------ blob codec, createCollation
+def _blob_tables(lists):
+    """lists of byte strings -> (flat uint8, blob_off uint64[nblobs+1], list_off uint64[n+1])"""
+    blobs = [bytes(b) for lst in lists for b in lst]
+    flat, blob_off = _pack(blobs)
+    list_off = np.zeros(len(lists) + 1, np.uint64)
+    list_off[1:] = np.cumsum([len(lst) for lst in lists])
+    return flat, blob_off, list_off
+
+
+def blob_serialized_size(blob_off, list_off) -> np.ndarray:
+    """Body offsets (n_lists + 1) of utils.Serialize over these lists (gsv.h gsv_blob_serialized_size):
+    host arithmetic, no GPU."""
+    blob_off = np.ascontiguousarray(blob_off, np.uint64)
+    list_off = np.ascontiguousarray(list_off, np.uint64)
+    out = np.zeros(list_off.shape[0], np.uint64)
+    check(_lib.load().gsv_blob_serialized_size(_ptr(blob_off), _ptr(list_off), list_off.shape[0] - 1, _ptr(out)))
+    return out
+
+
+def blob_data_layout(off) -> np.ndarray:
+    """Data-region offsets (n + 1) of the device-resident Deserialize (gsv.h gsv_blob_data_layout)."""
+    off = np.ascontiguousarray(off, np.uint64)
+    out = np.zeros(off.shape[0], np.uint64)
+    check(_lib.load().gsv_blob_data_layout(_ptr(off), off.shape[0] - 1, _ptr(out)))
+    return out
+
+
+def proposer_body_layout(blob_off, list_off):
+    """(body_off (n + 1), status (n,)) of createCollation's bodies (gsv.h gsv_proposer_body_layout): an
+    oversized collation has ST_BODY_TOO_LARGE and length 0."""
+    blob_off = np.ascontiguousarray(blob_off, np.uint64)
+    list_off = np.ascontiguousarray(list_off, np.uint64)
+    n = list_off.shape[0] - 1
+    out = np.zeros(n + 1, np.uint64)
+    st = np.zeros(n, np.uint8)
+    check(_lib.load().gsv_proposer_body_layout(_ptr(blob_off), _ptr(list_off), n, _ptr(out), _ptr(st)))
+    return out, st
+
+
+def _blob_serialize_batch(self, lists, skip_evm=None):
+    """utils.Serialize of each list of byte strings (gsv.h gsv_blob_serialize_batch): a list of bodies.
+    skip_evm: per list, the blobs' flags (None: all false)."""
+    n = len(lists)
+    if n == 0:
+        return []
+    flat, blob_off, list_off = _blob_tables(lists)
+    sk = None
+    if skip_evm is not None:
+        sk = np.array([1 if f else 0 for fl in skip_evm for f in fl] + [0], np.uint8)
+        if sk.shape[0] - 1 != blob_off.shape[0] - 1:
+            raise ValueError("skip_evm and blobs sizes differ")
+    body_off = blob_serialized_size(blob_off, list_off)
+    out = np.zeros(int(body_off[n]) + 1, np.uint8)
+    check(_lib.load().gsv_blob_serialize_batch(self._h, _ptr(flat), _ptr(blob_off), _ptr(sk) if sk is not None else None,
+                                               _ptr(list_off), n, _ptr(out), _ptr(body_off)))
+    return [out[int(body_off[i]):int(body_off[i + 1])].tobytes() for i in range(n)]
+
+
+def _blob_serialize_prepare(self, blob_off, list_off):
+    blob_off = np.ascontiguousarray(blob_off, np.uint64)
+    list_off = np.ascontiguousarray(list_off, np.uint64)
+    check(_lib.load().gsv_blob_serialize_prepare(self._h, _ptr(blob_off), _ptr(list_off), list_off.shape[0] - 1))
+
+
+def _blob_serialize_batch_dev(self, blobs_t, blob_off, list_off, bodies_t, skip_t=None, stream=None, prepare=True):
+    """blobs_t / skip_t / bodies_t: torch uint8 CUDA tensors; blob_off, list_off: numpy uint64 (host).
+    bodies_t follows blob_serialized_size's layout and is 16-byte aligned."""
+    blob_off = np.ascontiguousarray(blob_off, np.uint64)
+    list_off = np.ascontiguousarray(list_off, np.uint64)
+    if prepare:
+        _blob_serialize_prepare(self, blob_off, list_off)
+    sp = _sp(stream)
+    check(_lib.load().gsv_blob_serialize_batch_dev(self._h, _tptr(blobs_t), _ptr(blob_off), _tptr(skip_t),
+                                                   _ptr(list_off), list_off.shape[0] - 1, _tptr(bodies_t), sp))
+
+
+def _blob_deserialize_batch(self, bodies):
+    """utils.Deserialize of each body (gsv.h gsv_blob_deserialize_batch): per body, the list of
+    (blob bytes, skip_evm) the reference returns."""
+    n = len(bodies)
+    if n == 0:
+        return []
+    flat, off = _pack(bodies)
+    chunks = int(sum(len(b) // 32 for b in bodies))
+    nb = np.zeros(n, np.uint32)
+    boff = np.zeros(chunks + 1, np.uint64)
+    sk = np.zeros(chunks + 1, np.uint8)
+    data = np.zeros(31 * chunks + 1, np.uint8)
+    check(_lib.load().gsv_blob_deserialize_batch(self._h, _ptr(flat), _ptr(off), n, _ptr(nb), _ptr(boff), _ptr(sk),
+                                                 _ptr(data)))
+    out, k = [], 0
+    for i in range(n):
+        out.append([(data[int(boff[k + t]):int(boff[k + t + 1])].tobytes(), int(sk[k + t])) for t in range(int(nb[i]))])
+        k += int(nb[i])
+    return out
+
+
+def _blob_deserialize_prepare(self, h_off, max_blobs: int):
+    h_off = np.ascontiguousarray(h_off, np.uint64)
+    check(_lib.load().gsv_blob_deserialize_prepare(self._h, _ptr(h_off), h_off.shape[0] - 1, int(max_blobs)))
+
+
+def _blob_deserialize_batch_dev(self, bodies_t, h_off, max_blobs, nblobs_t, start_t, len_t, skip_t, data_t=None,
+                                stream=None, prepare=True):
+    """bodies_t: torch uint8 CUDA; nblobs_t (n,) / start_t, len_t (n, max_blobs) int32-sized; skip_t
+    (n, max_blobs) uint8; data_t: uint8, blob_data_layout's regions (None: index only)."""
+    h_off = np.ascontiguousarray(h_off, np.uint64)
+    if prepare:
+        _blob_deserialize_prepare(self, h_off, max_blobs)
+    sp = _sp(stream)
+    check(_lib.load().gsv_blob_deserialize_batch_dev(self._h, _tptr(bodies_t), _ptr(h_off), h_off.shape[0] - 1,
+                                                     int(max_blobs), _tptr(nblobs_t), _tptr(start_t), _tptr(len_t),
+                                                     _tptr(skip_t), _tptr(data_t), sp))
+
+
+def _proposer_create_collations(self, tx_lists, shard_id32, period32, proposer20, seckey32):
+    """proposer.createCollation over a batch (gsv.h gsv_proposer_create_collations): tx_lists[i] = the
+    encoded transactions of collation i; the other arrays (n, 32) / (n, 20) uint8.  Returns (bodies (list
+    of bytes), chunk_root (n,32), hash (n,32), sig (n,65), status (n,)).  The keys' device copy is
+    overwritten before the call returns."""
+    n = len(tx_lists)
+    sid = _np_u8(shard_id32).reshape(n, 32)
+    per = _np_u8(period32).reshape(n, 32)
+    prop = _np_u8(proposer20).reshape(n, 20)
+    keys = _seckey_rows(seckey32)
+    if keys.shape[0] != n:
+        raise ValueError("tx_lists and keys batch sizes differ")
+    root = np.zeros((n, 32), np.uint8)
+    h = np.zeros((n, 32), np.uint8)
+    sig = np.zeros((n, 65), np.uint8)
+    st = np.zeros(n, np.uint8)
+    if n == 0:
+        return [], root, h, sig, st
+    flat, blob_off, list_off = _blob_tables(tx_lists)
+    body_off, _ = proposer_body_layout(blob_off, list_off)
+    out = np.zeros(int(body_off[n]) + 1, np.uint8)
+    check(_lib.load().gsv_proposer_create_collations(self._h, _ptr(flat), _ptr(blob_off), _ptr(list_off), n, _ptr(sid),
+                                                     _ptr(per), _ptr(prop), _ptr(keys), _ptr(out), _ptr(body_off),
+                                                     _ptr(root), _ptr(h), _ptr(sig), _ptr(st)))
+    bodies = [out[int(body_off[i]):int(body_off[i + 1])].tobytes() for i in range(n)]
+    return bodies, root, h, sig, st
+
+
+def _proposer_prepare(self, blob_off, list_off):
+    blob_off = np.ascontiguousarray(blob_off, np.uint64)
+    list_off = np.ascontiguousarray(list_off, np.uint64)
+    check(_lib.load().gsv_proposer_prepare(self._h, _ptr(blob_off), _ptr(list_off), list_off.shape[0] - 1))
+
+
+def _proposer_create_collations_dev(self, blobs_t, blob_off, list_off, sid_t, per_t, prop_t, key_t, bodies_t, root_t,
+                                    hash_t, sig_t, st_t, stream=None, prepare=True):
+    """torch uint8 CUDA tensors (blob_off, list_off: numpy uint64 on the host); bodies_t follows
+    proposer_body_layout.  Only enqueues on `stream`; key_t is the caller's to wipe."""
+    blob_off = np.ascontiguousarray(blob_off, np.uint64)
+    list_off = np.ascontiguousarray(list_off, np.uint64)
+    if prepare:
+        _proposer_prepare(self, blob_off, list_off)
+    sp = _sp(stream)
+    check(_lib.load().gsv_proposer_create_collations_dev(
+        self._h, _tptr(blobs_t), _ptr(blob_off), _ptr(list_off), list_off.shape[0] - 1, _tptr(sid_t), _tptr(per_t),
+        _tptr(prop_t), _tptr(key_t), _tptr(bodies_t), _tptr(root_t), _tptr(hash_t), _tptr(sig_t), _tptr(st_t), sp))
+
+
+Context.blob_serialize_batch = _blob_serialize_batch
+Context.blob_serialize_prepare = _blob_serialize_prepare
+Context.blob_serialize_batch_dev = _blob_serialize_batch_dev
+Context.blob_deserialize_batch = _blob_deserialize_batch
+Context.blob_deserialize_prepare = _blob_deserialize_prepare
+Context.blob_deserialize_batch_dev = _blob_deserialize_batch_dev
+Context.proposer_create_collations = _proposer_create_collations
+Context.proposer_prepare = _proposer_prepare
+Context.proposer_create_collations_dev = _proposer_create_collations_dev

@@ -27,6 +27,7 @@ ST_BN_BAD_INPUT = 9
 ST_PROPOSER_MISMATCH = 10
 ST_INVALID_KEY = 11
 ST_INVALID_CURVE = 12
+ST_BODY_TOO_LARGE = 13
 
 # a short text per per-item status: the reference's error string where it has one (include/gsv.h names
 # the sources)
@@ -44,6 +45,7 @@ STATUS_STRINGS = {
     ST_PROPOSER_MISMATCH: "recovered signer is not the header's proposer",
     ST_INVALID_KEY: "invalid private key",
     ST_INVALID_CURVE: "ecies: invalid elliptic curve",
+    ST_BODY_TOO_LARGE: "serialized body size exceeds the collation size limit",
 }
 
 SIGNER_EIP155 = 0
@@ -166,6 +168,21 @@ SIGNATURES = [
                                                      ctypes.c_int, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
     ("gsv_notary_partition_unpack_dev", ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.c_uint32, _vp, _vp, _vp,
                                                        _vp, _vp]),
+    ("gsv_blob_serialized_size", ctypes.c_int, [_vp, _vp, _sz, _vp]),
+    ("gsv_blob_serialize_batch", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    ("gsv_blob_serialize_prepare", ctypes.c_int, [_vp, _vp, _vp, _sz]),
+    ("gsv_blob_serialize_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    ("gsv_blob_deserialize_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    ("gsv_blob_data_layout", ctypes.c_int, [_vp, _sz, _vp]),
+    ("gsv_blob_deserialize_prepare", ctypes.c_int, [_vp, _vp, _sz, ctypes.c_uint32]),
+    ("gsv_blob_deserialize_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _sz, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp,
+                                                      _vp]),
+    ("gsv_proposer_body_layout", ctypes.c_int, [_vp, _vp, _sz, _vp, _vp]),
+    ("gsv_proposer_create_collations", ctypes.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                      _vp, _vp, _vp]),
+    ("gsv_proposer_prepare", ctypes.c_int, [_vp, _vp, _vp, _sz]),
+    ("gsv_proposer_create_collations_dev", ctypes.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                          _vp, _vp, _vp]),
 ]
 
 _lib = None

@@ -10,6 +10,9 @@ batched on the GPU.
                                      SMCClient.Sign (sharding/mainchain/smc_client.go:245-248) at
                                      sharding/proposer/proposer.go:83 (the reference never checks it)
     SignHeaders(hdrs, keys)          that signature made: crypto.Sign over each unsigned header hash
+    Serialize / Deserialize          sharding/utils/marshal.go:71-198 (the blob codec)
+    SerializeTxToBlob / DeserializeBlobToTx   sharding/collation.go:158-206, over RLP-encoded transactions
+    CreateCollations(...)            proposer.createCollation (sharding/proposer/proposer.go:55-92) as a batch
 
 Integers (ShardID, Period) are Python ints (the reference's *big.Int); None stands for a nil pointer.
 """
@@ -167,6 +170,78 @@ def CalculatePOCBatch(bodies, salt: bytes, ctx=None) -> np.ndarray:
     return (ctx or default_context()).collation_poc_batch(list(bodies), bytes(salt))
 
 
+# ---------------------------------------------------------------- the producer side
+def Serialize(blobs, skip_evm=None, ctx=None) -> bytes:
+    """utils.Serialize (sharding/utils/marshal.go:71-123): blobs = byte strings, skip_evm = their flags
+    (None: all false).  A zero-length blob emits nothing, as in the reference.  No size limit."""
+    blobs = [bytes(b) for b in blobs]
+    if not blobs:
+        return b""
+    return (ctx or default_context()).blob_serialize_batch([blobs], None if skip_evm is None else [list(skip_evm)])[0]
+
+
+def Deserialize(body, ctx=None):
+    """utils.Deserialize (sharding/utils/marshal.go:144-198): the body's blobs as (bytes, skip_evm).  A
+    body past 2^20 bytes is refused (GsvError, GSV_E_TOO_LARGE): no collation body is larger."""
+    body = bytes(body)
+    if len(body) < 32:
+        return []
+    return (ctx or default_context()).blob_deserialize_batch([body])[0]
+
+
+def _size_error(size):
+    return ValueError("the serialized body size %d exceeded the collation size limit %d" % (size, COLLATION_SIZE_LIMIT))
+
+
+def SerializeTxToBlob(encoded_txs, ctx=None) -> bytes:
+    """sharding.SerializeTxToBlob (sharding/collation.go:158-174) over RLP-encoded transactions (skipEvm
+    false, convertTxToRawBlob); past 2^20 bytes it raises ValueError with the reference's message."""
+    txs = [bytes(t) for t in encoded_txs]
+    size = sum(32 * ((len(t) + 30) // 31) for t in txs)
+    if size > COLLATION_SIZE_LIMIT:
+        raise _size_error(size)
+    return Serialize(txs, None, ctx)
+
+
+def DeserializeBlobToTx(body, ctx=None):
+    """sharding.DeserializeBlobToTx (sharding/collation.go:193-206), up to the RLP decode: the encoded
+    transactions of a body."""
+    return [b for b, _ in Deserialize(body, ctx)]
+
+
+def CreateCollations(tx_lists, shard_ids, periods, proposers, keys, ctx=None):
+    """proposer.createCollation over a batch (sharding/proposer/proposer.go:55-92), one prepared GPU call:
+    tx_lists[i] = collation i's RLP-encoded transactions, shard_ids / periods ints, proposers 20-byte
+    addresses, keys the signers' secret keys (int or up to 32 big-endian bytes; account and signer are
+    separate in the reference, so the address is not derived from the key).  Returns [Collation] with the
+    body serialized, the chunk root set and the header signed over its hash with ProposerSignature empty.
+    A key that is no valid secret key raises crypto.ErrInvalidKey, a body past 2^20 bytes a ValueError
+    with SerializeTxToBlob's message; in both cases nothing is returned.  Not done here: the SMC checks of
+    createCollation (shard count, checkHeaderAdded) and AddHeader."""
+    from . import crypto
+    tx_lists = [[bytes(t) for t in lst] for lst in tx_lists]
+    n = len(tx_lists)
+    keys = [crypto._padded_key(k) for k in keys]
+    if not (len(shard_ids) == len(periods) == len(proposers) == len(keys) == n):
+        raise ValueError("batch sizes differ")
+    if n == 0:
+        return []
+    for p in proposers:
+        if len(bytes(p)) != 20:
+            raise ValueError("a proposer address is 20 bytes")
+    sid = np.frombuffer(b"".join(_int32(x) for x in shard_ids), np.uint8).reshape(n, 32)
+    per = np.frombuffer(b"".join(_int32(x) for x in periods), np.uint8).reshape(n, 32)
+    prop = np.frombuffer(b"".join(bytes(p) for p in proposers), np.uint8).reshape(n, 20)
+    key = np.frombuffer(b"".join(keys), np.uint8).reshape(n, 32)
+    bodies, root, _, sig, st = (ctx or default_context()).proposer_create_collations(tx_lists, sid, per, prop, key)
+    for i in np.flatnonzero(st == _lib.ST_BODY_TOO_LARGE):
+        raise _size_error(sum(32 * ((len(t) + 30) // 31) for t in tx_lists[int(i)]))
+    if (st != _lib.ST_OK).any():
+        raise crypto.ErrInvalidKey("invalid private key (collation %d)" % int(np.flatnonzero(st != _lib.ST_OK)[0]))
+    return [Collation(CollationHeader(shard_ids[i], bytes(root[i]), periods[i], bytes(proposers[i]), bytes(sig[i])),
+                      bodies[i], list(tx_lists[i])) for i in range(n)]
+
+
 __all__ = ["DeriveSha", "DeriveShaBatch", "CollationHeader", "Collation", "HeaderHashBatch",
            "VerifyProposerSignatures", "CalculatePOCBatch", "ErrProposerMismatch", "COLLATION_SIZE_LIMIT",
-           "_lib"]
+           "Serialize", "Deserialize", "SerializeTxToBlob", "DeserializeBlobToTx", "CreateCollations", "_lib"]

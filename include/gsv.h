@@ -42,6 +42,12 @@
  *   gsv_collation_header_verify_batch <- CollationHeader.Hash (sharding/collation.go:66-71) and the
  *                                 proposer signature made by SMCClient.Sign (sharding/mainchain/
  *                                 smc_client.go:245-248, signed at sharding/proposer/proposer.go:83)
+ *   gsv_blob_serialize_batch   <- utils.Serialize (sharding/utils/marshal.go:71-123), behind
+ *                                 sharding.SerializeTxToBlob (sharding/collation.go:158-174)
+ *   gsv_blob_deserialize_batch <- utils.Deserialize (sharding/utils/marshal.go:144-198), behind
+ *                                 sharding.DeserializeBlobToTx (sharding/collation.go:193-206)
+ *   gsv_proposer_create_collations <- proposer.createCollation (sharding/proposer/proposer.go:55-92):
+ *                                 SerializeTxToBlob, CalculateChunkRoot, Hash(), SMCClient.Sign
  *
  *   gsv_ecrecover_precompile_batch <- the ecrecover precompile's Run (core/vm/contracts.go:78-101)
  *   gsv_bn256_add_batch        <- the bn256Add precompile's Run (core/vm/contracts.go:274-289)
@@ -107,6 +113,7 @@ extern "C" {
 #define GSV_ST_PROPOSER_MISMATCH 10 /* recovered signer != header ProposerAddress */
 #define GSV_ST_INVALID_KEY 11      /* secp256k1.ErrInvalidKey          secp256.go:58 */
 #define GSV_ST_INVALID_CURVE 12    /* ecies.ErrInvalidCurve            ecies/ecies.go:47 */
+#define GSV_ST_BODY_TOO_LARGE 13   /* SerializeTxToBlob's size error   sharding/collation.go:169-171 */
 
 /* signer kinds for gsv_tx_sender_batch (core/types/transaction_signing.go) */
 #define GSV_SIGNER_EIP155 0
@@ -485,6 +492,96 @@ int gsv_collation_header_verify_batch_dev(gsv_ctx *ctx, const uint8_t *d_shard_i
                                           const uint8_t *d_sig65, const uint8_t *d_nil_flags, size_t n,
                                           uint8_t *d_hash32_out, uint8_t *d_signer20_out, uint8_t *d_status,
                                           void *stream);
+
+/* ---- blob codec: utils.Serialize / utils.Deserialize (sharding/utils/marshal.go:71-198) ----
+ * Serialize.  List i (one collation) holds blobs [list_off[i], list_off[i+1]) of the global blob array;
+ * blob k = blobs[blob_off[k] .. blob_off[k+1]) with flag skip_evm[k] (skip_evm NULL: all false).  Body i is
+ * the concatenation of each blob's ceil(len / 31) chunks of 32 bytes: a non-terminal chunk is 00 and 31
+ * data bytes, the terminal chunk is tl | (skip_evm ? 0x80 : 0) with tl = len - 31 (chunks - 1), tl data
+ * bytes and 31 - tl zero bytes.  A ZERO-LENGTH BLOB EMITS NOTHING (getNumChunks(0) = 0), as in the
+ * reference: Deserialize never gives that blob back.  No size limit here (the 2^20 limit is
+ * SerializeTxToBlob's: see the proposer below); blobs of less than 2^32 bytes, fewer than 2^31 chunks per
+ * call (GSV_E_TOO_LARGE).  The bodies lie contiguous at body_off_out[0 .. n_lists], each a multiple of 32.
+ * gsv_blob_serialized_size is host arithmetic alone (no context, no GPU): body_off_out[n_lists + 1]. */
+int gsv_blob_serialized_size(const uint64_t *blob_off, const uint64_t *list_off, size_t n_lists,
+                             uint64_t *body_off_out);
+int gsv_blob_serialize_batch(gsv_ctx *ctx, const uint8_t *blobs, const uint64_t *blob_off, const uint8_t *skip_evm,
+                             const uint64_t *list_off, size_t n_lists, uint8_t *bodies_out, uint64_t *body_off_out);
+/* Device-resident form: d_blobs and d_skip_evm (may be NULL) in HBM, the offset tables on the host;
+ * d_bodies_out (16-byte aligned, gsv_blob_serialized_size's layout) in HBM.  One launch on `stream`; no
+ * byte outside d_blobs[blob_off[list_off[0]] .. blob_off[list_off[n_lists]]) is read.
+ * gsv_blob_serialize_prepare builds the chunk tables for exactly (blob_off, list_off). */
+int gsv_blob_serialize_prepare(gsv_ctx *ctx, const uint64_t *blob_off, const uint64_t *list_off, size_t n_lists);
+int gsv_blob_serialize_batch_dev(gsv_ctx *ctx, const uint8_t *d_blobs, const uint64_t *blob_off,
+                                 const uint8_t *d_skip_evm, const uint64_t *list_off, size_t n_lists,
+                                 uint8_t *d_bodies_out, void *stream);
+/* Deserialize.  Body i = bodies[off[i] .. off[i+1]), at most 2^20 bytes (GSV_E_TOO_LARGE), at most 65,535
+ * bodies.  Only whole chunks count (a trailing partial chunk is ignored); a chunk whose indicator & 0x1F
+ * is tl != 0 ends a blob of 31 (chunks - 1) + tl bytes, indicator bit 7 is its skip_evm flag and no other
+ * indicator bit is read; chunks after the last terminal chunk are dropped.
+ * Host form: the reference's list of byte strings.  nblobs_out[i] = blobs of body i; the blobs of all
+ * bodies in order are data_out[blob_off_out[k] .. blob_off_out[k+1]) with flag skip_evm_out[k].  Size
+ * blob_off_out for sum(floor(len_i / 32)) + 1 entries, skip_evm_out for that many less one, data_out for
+ * 31 sum(floor(len_i / 32)) bytes. */
+int gsv_blob_deserialize_batch(gsv_ctx *ctx, const uint8_t *bodies, const uint64_t *off, size_t n,
+                               uint32_t *nblobs_out, uint64_t *blob_off_out, uint8_t *skip_evm_out,
+                               uint8_t *data_out);
+/* Device-resident form, 1 <= max_blobs <= GSV_MAX_TXS_PER_SHARD.  d_nblobs[i] = the true blob count of
+ * body i, also when it exceeds max_blobs; rows [n][max_blobs] of d_blob_start / d_blob_len (uint32) and
+ * d_skip_evm (bytes): blob t < min(nblobs, max_blobs) of body i lies at d_data[data_off[i] + blob_start ..
+ * + blob_len), later rows are zero.  d_data (may be NULL: index only; 16-byte aligned) holds, per body,
+ * every chunk's 31 data bytes at 31 c of the body's data region (so blob_start = 31 first_chunk and no
+ * second pass is needed); FILLER BYTES ARE COPIED AS THEY STAND in the body, between one blob's end and
+ * the next blob's start.  gsv_blob_data_layout (host arithmetic alone) gives data_off[n + 1]: regions of
+ * 31 floor(len / 32) bytes padded to 16, the padding written as zeros. */
+int gsv_blob_data_layout(const uint64_t *off, size_t n, uint64_t *data_off_out);
+int gsv_blob_deserialize_prepare(gsv_ctx *ctx, const uint64_t *h_off, size_t n, uint32_t max_blobs);
+int gsv_blob_deserialize_batch_dev(gsv_ctx *ctx, const uint8_t *d_bodies, const uint64_t *h_off, size_t n,
+                                   uint32_t max_blobs, uint32_t *d_nblobs, uint32_t *d_blob_start,
+                                   uint32_t *d_blob_len, uint8_t *d_skip_evm, uint8_t *d_data, void *stream);
+
+/* ---- proposer.createCollation (sharding/proposer/proposer.go:55-92) ----
+ * Collation i: its encoded transactions are blobs [list_off[i], list_off[i+1]) as above (skip_evm false,
+ * convertTxToRawBlob), its header fields shard_id32[i] / period32[i] (32-byte big-endian) and
+ * proposer20[i], and the signer's secret key seckey32[i] (the reference takes account and signer
+ * separately, and so does this call: the address is not derived from the key).  Per collation:
+ *   body           SerializeTxToBlob(txs), at body_off_out[i]: gsv_blob_serialized_size's layout with every
+ *                  oversized collation's length 0 (gsv_proposer_body_layout: host arithmetic alone)
+ *   chunk_root32   CalculateChunkRoot(); emptyRoot for an empty transaction list
+ *   hash32         CollationHeader.Hash() with ProposerSignature empty: what proposer.go:83 signs
+ *   sig65          crypto.Sign(hash32, key) = [R || S || V], as gsv_ecdsa_sign_batch returns it
+ *   status         GSV_ST_OK; GSV_ST_INVALID_KEY (key 0 or >= n: sig65 zero, body, root and hash still
+ *                  produced); GSV_ST_BODY_TOO_LARGE (serialized size > 2^20, collation.go:169-171: a
+ *                  zero-length body and zero root, hash and signature; the rest of the batch proceeds)
+ * At most 65,535 collations per call.  Steps on the GPU: the serialize kernel, the chunk roots of the
+ * bodies it wrote, the header-hash kernel reading those roots, the signing kernel.
+ * Secret keys: as for gsv_ecdsa_sign_batch.  The host form stages the keys FIRST in the context's device
+ * arena (offset 0) and overwrites that copy, on the context stream and before its final synchronisation,
+ * on every return that follows the copy-in (error returns included); it keeps no host copy.  The _dev form
+ * reads the caller's device buffer and writes no key material anywhere; wiping that buffer is the caller's.
+ * What this path does NOT promise (compare crypto/signature_cgo.go:48-51 on its own caveat): the
+ * fixed-base multiplication indexes a 1 GB table in HBM by 20-bit digits of the secret nonce, and the
+ * low-s step branches on a bit derived from secrets; libsecp256k1's ecmult_gen is blinded and scans its
+ * whole table.  So the path is NOT hardened against a co-tenant that observes timing or memory traffic
+ * on the same GPU.  The nonce's inversion mod n is the constant-time one.  Nor does the library control
+ * what the HIP runtime's own host-to-device staging buffer holds after a copy from pageable memory. */
+int gsv_proposer_body_layout(const uint64_t *blob_off, const uint64_t *list_off, size_t n, uint64_t *body_off_out,
+                             uint8_t *status_out);
+int gsv_proposer_create_collations(gsv_ctx *ctx, const uint8_t *blobs, const uint64_t *blob_off,
+                                   const uint64_t *list_off, size_t n, const uint8_t *shard_id32,
+                                   const uint8_t *period32, const uint8_t *proposer20, const uint8_t *seckey32,
+                                   uint8_t *bodies_out, uint64_t *body_off_out, uint8_t *chunk_root32_out,
+                                   uint8_t *hash32_out, uint8_t *sig65_out, uint8_t *status);
+/* Device-resident form: every array in HBM except the two offset tables; d_bodies_out 16-byte aligned.
+ * Only enqueues on `stream`; gsv_proposer_prepare prepares it for exactly (blob_off, list_off): the
+ * serialize tables, the trie plans of the bodies' lengths and the workspace.  Prepared at pipeline depth
+ * D, D calls on D streams run concurrently. */
+int gsv_proposer_prepare(gsv_ctx *ctx, const uint64_t *blob_off, const uint64_t *list_off, size_t n);
+int gsv_proposer_create_collations_dev(gsv_ctx *ctx, const uint8_t *d_blobs, const uint64_t *blob_off,
+                                       const uint64_t *list_off, size_t n, const uint8_t *d_shard_id32,
+                                       const uint8_t *d_period32, const uint8_t *d_proposer20,
+                                       const uint8_t *d_seckey32, uint8_t *d_bodies_out, uint8_t *d_chunk_root32,
+                                       uint8_t *d_hash32, uint8_t *d_sig65, uint8_t *d_status, void *stream);
 
 /* ---- multi-GPU: the shard partition and its one collective ----
  * One process per GPU.  Rank r of N owns the contiguous shard block [floor(S r / N), floor(S (r+1) / N))
