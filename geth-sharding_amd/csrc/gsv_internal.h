@@ -37,6 +37,19 @@ hipError_t launch_pubkey_create(const uint8_t* seckey32, uint32_t n, const uint4
 hipError_t launch_ecdh(const uint8_t* point64, const uint8_t* scalar32, uint32_t n, uint8_t* xy64, uint8_t* x32,
                        uint8_t* keys48, uint8_t* status, hipStream_t st);
 
+// ecies.hip: the launches of Decrypt / Encrypt around launch_ecdh (launch_pubkey_create too for
+// Encrypt).  work: the caller's area they share, no padding between its parts (ecies.hip draws it):
+// ECIES_WORK_DEC / ECIES_WORK_ENC bytes per item
+constexpr size_t ECIES_WORK_DEC = 48 + 64 + 1, ECIES_WORK_ENC = 48 + 65 + 1 + 1;
+hipError_t launch_ecies_parse(const uint8_t* ct, const uint64_t* ct_off, const uint8_t* seckey32, uint32_t n,
+                              uint8_t* point64, uint8_t* status, hipStream_t st);
+hipError_t launch_ecies_open(const uint8_t* ct, const uint64_t* ct_off, const uint8_t* s2, const uint64_t* s2_off,
+                             uint32_t n, uint8_t* work, uint8_t* msg_out, uint32_t* msg_len, uint8_t* status,
+                             hipStream_t st);
+hipError_t launch_ecies_seal(const uint8_t* msg, const uint64_t* msg_off, const uint8_t* iv16, const uint8_t* s2,
+                             const uint64_t* s2_off, uint32_t n, uint8_t* work, uint8_t* ct_out, uint8_t* status,
+                             hipStream_t st);
+
 // keccak.hip
 hipError_t launch_keccak256(const uint8_t* data, const uint64_t* off, uint32_t n, uint8_t* out32,
                             hipStream_t st);

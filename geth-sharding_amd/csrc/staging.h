@@ -93,6 +93,38 @@ struct EcdhStage {
         : key(L.buf(n * 32)), shared(L.buf(n * 32, want_shared)), keys(L.buf(n * 48, want_keys)), secret(L.n),
           pt(L.buf(n * 64)), st(L.buf(n)) {}
 };
+// gsv_ecies_decrypt_batch, gsv_ecies_encrypt_batch.  The same rule: the secret (or ephemeral) keys, the
+// work area the launches share (Ke || Km) and the plaintext (Decrypt's output, Encrypt's input) come
+// FIRST and contiguous, `secret` is their end, and the host form overwrites [0, secret).  `work` is
+// work_per bytes per item (gsv_ecies_work_bytes); s2 and its offset table are absent when the caller
+// passes none.
+struct EciesDecryptStage {
+    B8 key, work, msg;
+    size_t secret;
+    B8 ct;
+    Buf<uint64_t> off;
+    B8 s2;
+    Buf<uint64_t> s2off;
+    Buf<uint32_t> mlen;
+    B8 st;
+    EciesDecryptStage(Layout& L, size_t n, size_t work_per, size_t bytes, size_t s2_bytes, bool has_s2)
+        : key(L.buf(n * 32)), work(L.buf(n * work_per)), msg(L.buf(bytes)), secret(L.n), ct(L.buf(bytes)),
+          off(L.buf<uint64_t>((n + 1) * 8)), s2(L.buf(s2_bytes, has_s2)), s2off(L.buf<uint64_t>((n + 1) * 8, has_s2)),
+          mlen(L.buf<uint32_t>(n * 4)), st(L.buf(n)) {}
+};
+struct EciesEncryptStage {
+    B8 key, work, msg;
+    size_t secret;
+    B8 pub, iv;
+    Buf<uint64_t> off;
+    B8 s2;
+    Buf<uint64_t> s2off;
+    B8 ct, st;
+    EciesEncryptStage(Layout& L, size_t n, size_t work_per, size_t bytes, size_t s2_bytes, bool has_s2)
+        : key(L.buf(n * 32)), work(L.buf(n * work_per)), msg(L.buf(bytes)), secret(L.n), pub(L.buf(n * 64)),
+          iv(L.buf(n * 16)), off(L.buf<uint64_t>((n + 1) * 8)), s2(L.buf(s2_bytes, has_s2)),
+          s2off(L.buf<uint64_t>((n + 1) * 8, has_s2)), ct(L.buf(bytes + n * 113)), st(L.buf(n)) {}
+};
 // fixed-size records in, fixed-size results and a status byte out: gsv_ecrecover_precompile_batch
 // (128 -> 32), bn_g1_host (128 or 96 -> 64)
 struct RecordStage {

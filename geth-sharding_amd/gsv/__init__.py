@@ -842,6 +842,87 @@ def _ecdh_batch_dev(self, pub_t, key_t, shared_t, keys_t, st_t, stream=None):
                                          _tptr(st_t), sp))
 
 
+def _s2_tables(s2s, n):
+    """per-item s2 byte strings (or None: every s2 empty) -> (flat, off) or (None, None)"""
+    if s2s is None:
+        return None, None
+    if len(s2s) != n:
+        raise ValueError("one s2 per item (or None)")
+    return _pack([b"" if s is None else s for s in s2s])
+
+
+def _ecies_decrypt_batch(self, cts, keys, s2s=None):
+    """ecies.PrivateKey.Decrypt over a batch (gsv.h gsv_ecies_decrypt_batch): cts a list of ciphertexts, keys
+    (n,32) uint8 big-endian secret keys, s2s a list of byte strings or None.  Returns (msgs, status (n,)):
+    msgs[i] is the message (b"" where the status is not ST_OK).  The device copies of the keys, the derived
+    keys and the plaintext are overwritten before the call returns."""
+    keys = _seckey_rows(keys)
+    n = len(cts)
+    if keys.shape[0] != n:
+        raise ValueError("cts and keys batch sizes differ")
+    flat, off = _pack(cts)
+    s2, s2off = _s2_tables(s2s, n)
+    out = np.zeros(int(off[-1]) + 1, np.uint8)
+    mlen = np.zeros(n, np.uint32)
+    st = np.zeros(n, np.uint8)
+    if n:
+        check(_lib.load().gsv_ecies_decrypt_batch(self._h, _ptr(flat), _ptr(off), _ptr(keys), _ptr(s2), _ptr(s2off), n,
+                                                  _ptr(out), _ptr(mlen), _ptr(st)))
+    return [out[int(off[i]):int(off[i]) + int(mlen[i])].tobytes() for i in range(n)], st
+
+
+def _ecies_encrypt_batch(self, msgs, pubs, ephs, ivs, s2s=None):
+    """ecies.Encrypt over a batch (gsv.h gsv_ecies_encrypt_batch): msgs a list of messages, pubs (n,64) uint8
+    recipient points X || Y, ephs (n,32) ephemeral secret keys, ivs (n,16).  Returns (cts, status (n,)): cts[i]
+    is 04 || R || iv || ciphertext || tag (113 + len(m) zero bytes where the status is not ST_OK)."""
+    pubs = _point_rows(pubs)
+    ephs = _seckey_rows(ephs)
+    ivs = np.ascontiguousarray(ivs, np.uint8).reshape(-1, 16)
+    n = len(msgs)
+    if not (pubs.shape[0] == ephs.shape[0] == ivs.shape[0] == n):
+        raise ValueError("msgs, pubs, ephs and ivs batch sizes differ")
+    flat, off = _pack(msgs)
+    s2, s2off = _s2_tables(s2s, n)
+    out = np.zeros(int(off[-1]) + _lib.ECIES_OVERHEAD * n, np.uint8)
+    st = np.zeros(n, np.uint8)
+    if n:
+        check(_lib.load().gsv_ecies_encrypt_batch(self._h, _ptr(flat), _ptr(off), _ptr(pubs), _ptr(ephs), _ptr(ivs),
+                                                  _ptr(s2), _ptr(s2off), n, _ptr(out), _ptr(st)))
+    pos = [int(off[i]) + _lib.ECIES_OVERHEAD * i for i in range(n + 1)]
+    return [out[pos[i]:pos[i + 1]].tobytes() for i in range(n)], st
+
+
+def ecies_work_bytes(n: int, encrypt: bool) -> int:
+    """bytes of the work area the ecies *_dev forms need (gsv.h gsv_ecies_work_bytes)"""
+    return int(_lib.load().gsv_ecies_work_bytes(n, 1 if encrypt else 0))
+
+
+def _ecies_decrypt_batch_dev(self, ct_t, ct_off_t, key_t, s2_t, s2_off_t, msg_t, mlen_t, st_t, work_t, stream=None):
+    """torch CUDA tensors: ct_t uint8 ciphertexts back to back, ct_off_t (n+1,) int64 offsets into it, key_t (n,32),
+    s2_t / s2_off_t likewise or both None, msg_t uint8 (the slots: as long as ct_t), mlen_t (n,) int32, st_t (n,)
+    uint8, work_t uint8 of ecies_work_bytes(n, False) bytes (left all zero).  Only enqueues on `stream`."""
+    n = key_t.shape[0]
+    if ct_off_t.numel() != n + 1 or work_t.numel() < ecies_work_bytes(n, False):
+        raise ValueError("ct_off_t holds n + 1 offsets; work_t holds ecies_work_bytes(n, False) bytes")
+    sp = _sp(stream)
+    check(_lib.load().gsv_ecies_decrypt_batch_dev(self._h, _tptr(ct_t), _tptr(ct_off_t), _tptr(key_t), _tptr(s2_t),
+                                                  _tptr(s2_off_t), n, _tptr(msg_t), _tptr(mlen_t), _tptr(st_t),
+                                                  _tptr(work_t), sp))
+
+
+def _ecies_encrypt_batch_dev(self, msg_t, msg_off_t, pub_t, eph_t, iv_t, s2_t, s2_off_t, ct_t, st_t, work_t, stream=None):
+    """torch CUDA tensors: msg_t uint8 messages back to back, msg_off_t (n+1,) int64, pub_t (n,64), eph_t (n,32),
+    iv_t (n,16), s2_t / s2_off_t or both None, ct_t uint8 (item i at msg_off[i] + 113 i), st_t (n,), work_t uint8
+    of ecies_work_bytes(n, True) bytes (left all zero).  Only enqueues on `stream`."""
+    n = pub_t.shape[0]
+    if msg_off_t.numel() != n + 1 or work_t.numel() < ecies_work_bytes(n, True):
+        raise ValueError("msg_off_t holds n + 1 offsets; work_t holds ecies_work_bytes(n, True) bytes")
+    sp = _sp(stream)
+    check(_lib.load().gsv_ecies_encrypt_batch_dev(self._h, _tptr(msg_t), _tptr(msg_off_t), _tptr(pub_t), _tptr(eph_t),
+                                                  _tptr(iv_t), _tptr(s2_t), _tptr(s2_off_t), n, _tptr(ct_t), _tptr(st_t),
+                                                  _tptr(work_t), sp))
+
+
 def _arena_read(self, off, n):
     """Test hook (gsv.h gsv_ctx_arena_read): n bytes of the staging arena from `off`, as they are now."""
     out = np.zeros(n, np.uint8)
@@ -870,6 +951,10 @@ Context.secp256k1_scalar_mul_batch = _secp256k1_scalar_mul_batch
 Context.secp256k1_scalar_mul_batch_dev = _secp256k1_scalar_mul_batch_dev
 Context.ecdh_batch = _ecdh_batch
 Context.ecdh_batch_dev = _ecdh_batch_dev
+Context.ecies_decrypt_batch = _ecies_decrypt_batch
+Context.ecies_encrypt_batch = _ecies_encrypt_batch
+Context.ecies_decrypt_batch_dev = _ecies_decrypt_batch_dev
+Context.ecies_encrypt_batch_dev = _ecies_encrypt_batch_dev
 Context._arena_read = _arena_read
 Context.prepared_shapes = _prepared_shapes
 Context.bn256_add_batch = _bn256_add_batch

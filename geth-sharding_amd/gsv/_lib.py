@@ -28,6 +28,7 @@ ST_PROPOSER_MISMATCH = 10
 ST_INVALID_KEY = 11
 ST_INVALID_CURVE = 12
 ST_BODY_TOO_LARGE = 13
+ST_INVALID_MESSAGE = 14
 
 # a short text per per-item status: the reference's error string where it has one (include/gsv.h names
 # the sources)
@@ -46,6 +47,7 @@ STATUS_STRINGS = {
     ST_INVALID_KEY: "invalid private key",
     ST_INVALID_CURVE: "ecies: invalid elliptic curve",
     ST_BODY_TOO_LARGE: "serialized body size exceeds the collation size limit",
+    ST_INVALID_MESSAGE: "ecies: invalid message",
 }
 
 SIGNER_EIP155 = 0
@@ -68,6 +70,9 @@ K_NOTARY = 8
 K_DERIVE_LEAF = 9
 K_HEADER = 10
 K_BN_G1 = 11
+K_ECIES = 12
+
+ECIES_OVERHEAD = 113  # GSV_ECIES_OVERHEAD: 65 (R) + 16 (IV) + 32 (tag)
 
 # API errors (negative return values)
 E_INVALID_ARG = -1
@@ -114,6 +119,11 @@ SIGNATURES = [
     ("gsv_ecdh_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     ("gsv_ecdh_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("gsv_ctx_arena_read", ctypes.c_int, [_vp, _sz, _sz, _vp]),
+    ("gsv_ecies_decrypt_batch", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    ("gsv_ecies_encrypt_batch", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    ("gsv_ecies_work_bytes", _sz, [_sz, ctypes.c_int]),
+    ("gsv_ecies_decrypt_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    ("gsv_ecies_encrypt_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("gsv_sender_batch", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_int, _vp, _vp]),
     ("gsv_tx_sender_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, ctypes.c_int, _vp, _vp]),
     ("gsv_chunk_root_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp]),

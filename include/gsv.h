@@ -25,6 +25,9 @@
  *   gsv_ecdh_batch             <- ecies.PrivateKey.GenerateShared (crypto/ecies/ecies.go:121-138) and the
  *                                 key derivation of ecies.Encrypt / Decrypt (ecies.go:264-277, 347-356);
  *                                 the RLPx handshake's two GenerateShared calls (p2p/rlpx.go:243, 276)
+ *   gsv_ecies_decrypt_batch / gsv_ecies_encrypt_batch <- ecies.PrivateKey.Decrypt / ecies.Encrypt
+ *                                 (crypto/ecies/ecies.go:246-366): the RLPx handshake packets
+ *                                 (p2p/rlpx.go:434-511), whisper's asymmetric envelopes
  *   gsv_sender_batch           <- recoverPlain (core/types/transaction_signing.go:222-247)
  *                                 + crypto.ValidateSignatureValues (crypto/crypto.go:181-192)
  *   gsv_tx_sender_batch        <- types.Sender(signer, tx) (core/types/transaction_signing.go:72-89,
@@ -114,6 +117,7 @@ extern "C" {
 #define GSV_ST_INVALID_KEY 11      /* secp256k1.ErrInvalidKey          secp256.go:58 */
 #define GSV_ST_INVALID_CURVE 12    /* ecies.ErrInvalidCurve            ecies/ecies.go:47 */
 #define GSV_ST_BODY_TOO_LARGE 13   /* SerializeTxToBlob's size error   sharding/collation.go:169-171 */
+#define GSV_ST_INVALID_MESSAGE 14  /* ecies.ErrInvalidMessage          ecies/ecies.go:143 */
 
 /* signer kinds for gsv_tx_sender_batch (core/types/transaction_signing.go) */
 #define GSV_SIGNER_EIP155 0
@@ -152,7 +156,11 @@ int gsv_ctx_set_timing(gsv_ctx *ctx, int enable);
 #define GSV_K_DERIVE_LEAF 9 /* generic DeriveSha leaf encode + hash */
 #define GSV_K_HEADER 10    /* collation header hashing + signer comparison */
 #define GSV_K_BN_G1 11     /* bn256Add / bn256ScalarMul: one launch per call */
-#define GSV_K_COUNT 12
+#define GSV_K_COUNT 12     /* the ids above */
+/* Ids added behind GSV_K_COUNT (its value is part of ABI 2); gsv_ctx_kernel_time takes every id below
+ * GSV_K_END. */
+#define GSV_K_ECIES 12     /* the message half of ECIES: tag + AES-128-CTR, one launch per call */
+#define GSV_K_END 13
 /* total milliseconds and launch count accumulated for kernel `kid` since the last reset */
 int gsv_ctx_kernel_time(gsv_ctx *ctx, int kid, double *total_ms, long *launches);
 int gsv_ctx_reset_timing(gsv_ctx *ctx);
@@ -319,6 +327,77 @@ int gsv_ecdh_batch_dev(gsv_ctx *ctx, const uint8_t *d_pub64, const uint8_t *d_se
  * they are now, to `out` (GSV_E_INVALID_ARG past the arena's end).  The host forms above stage their
  * secrets from offset 0. */
 int gsv_ctx_arena_read(gsv_ctx *ctx, size_t off, size_t n, uint8_t *out);
+
+/* ---- ecies.Encrypt and PrivateKey.Decrypt (crypto/ecies/ecies.go:246-366) ----
+ * The whole of both for ECIES_AES128_SHA256 (params.go:69-76), byte for byte the reference's: the key
+ * agreement of gsv_ecdh_batch, then AES-128-CTR and the HMAC-SHA256 tag.  s1 (the KDF's shared
+ * information) is always empty and is not a parameter: every caller in the reference passes nil.  s2
+ * (the MAC's, e.g. RLPx's EIP-8 size prefix) is per item: item i's is s2[s2_off[i] .. s2_off[i+1]);
+ * s2 and s2_off both NULL means every s2 is empty.  An item of 2^32 bytes or more: GSV_E_TOO_LARGE.
+ *
+ * Decrypt.  Item i is c = ct[ct_off[i] .. ct_off[i+1]).  The checks run in the reference's order and the
+ * first failure decides the status:
+ *    1. len(c) == 0                                  GSV_ST_INVALID_MESSAGE
+ *    2. c[0] not 2, 3 or 4                           GSV_ST_INVALID_PUBKEY, whatever the length
+ *    3. len(c) < 98                                  GSV_ST_INVALID_MESSAGE
+ *    4. c[0] is 2 or 3                               GSV_ST_INVALID_PUBKEY: rLen is 65 for all three, and
+ *                                                    elliptic.Unmarshal takes only 04 || X || Y
+ *    5. X or Y >= p                                  GSV_ST_INVALID_PUBKEY.  A decision, not a reading: what
+ *       elliptic.Unmarshal does with such a coordinate depends on the Go release, and that code is not in
+ *       the reference tree.  No release yields a different plaintext; refusing is the strict reading.
+ *    6. Y^2 != X^3 + 7                               GSV_ST_INVALID_CURVE (ecies.go:337)
+ *    7. secret key 0 or >= n                         GSV_ST_INVALID_KEY
+ *    8. 98 <= len(c) < 113                           GSV_ST_INVALID_MESSAGE.  em is shorter than an IV: the
+ *       reference fails the tag there or, with a matching tag, panics in symDecrypt.
+ *    9. tag != HMAC-SHA256(Km, c[65 : len-32] || s2) GSV_ST_INVALID_MESSAGE
+ *   10. else GSV_ST_OK: the message is c[81 : len-32] XOR the AES-128-CTR keystream of Ke from the counter
+ *       block c[65:81], which is Go's cipher.NewCTR: one 128-bit big-endian integer, incremented with
+ *       carry through all 16 bytes.  len(c) == 113 is a valid empty message.
+ * Item i owns the slot msg_out[ct_off[i] .. ct_off[i+1]), and the call writes every byte of it: the
+ * message, then zeros; msg_len[i] = len(c) - 113.  A failed item's slot is all zeros and its msg_len 0;
+ * no plaintext byte of an item whose tag failed is left anywhere the call wrote.  msg_out does not
+ * overlap ct.
+ *
+ * Encrypt, with the two things the reference draws from rand supplied by the caller: the ephemeral
+ * secret key and the IV.  Item i: m = msg[msg_off[i] .. msg_off[i+1]) to the point pub64[i] (X || Y):
+ *   ct_i = 04 || eph G || iv || CTR(Ke, iv, m) || HMAC-SHA256(Km, iv || CTR(..) || s2),
+ * written at ct_out + msg_off[i] + 113 i (GSV_ECIES_OVERHEAD = 65 + 16 + 32, eciesOverhead of
+ * p2p/rlpx.go:58).  An ephemeral key of 0 or >= n gets GSV_ST_INVALID_KEY; else a recipient point off
+ * the curve GSV_ST_INVALID_CURVE (gsv_ecdh_batch's divergence: the reference's Encrypt does not check);
+ * else an empty message GSV_ST_INVALID_MESSAGE (the reference returns (nil, nil), ecies.go:280).  A
+ * failed item's 113 + len(m) bytes are zeros.
+ *
+ * Secrets: the secret and ephemeral keys, Ke || Km and the plaintext.  The host forms stage them FIRST
+ * in the context's device arena (keys, the work area, the plaintext), contiguous from offset 0, and
+ * overwrite that region on the context stream, before their final synchronisation, on every return
+ * that follows the copy-in (error returns included).  The caveats of the Sign and ECDH blocks above
+ * hold, and one more: the AES tables are indexed by key-dependent bytes. */
+#define GSV_ECIES_OVERHEAD 113
+int gsv_ecies_decrypt_batch(gsv_ctx *ctx, const uint8_t *ct, const uint64_t *ct_off, const uint8_t *seckey32,
+                            const uint8_t *s2, const uint64_t *s2_off, size_t n, uint8_t *msg_out,
+                            uint32_t *msg_len, uint8_t *status);
+int gsv_ecies_encrypt_batch(gsv_ctx *ctx, const uint8_t *msg, const uint64_t *msg_off, const uint8_t *pub64,
+                            const uint8_t *eph_seckey32, const uint8_t *iv16, const uint8_t *s2,
+                            const uint64_t *s2_off, size_t n, uint8_t *ct_out, uint8_t *status);
+/* Device-resident forms: every array in HBM, the offset tables included (as for gsv_keccak256_batch_dev);
+ * every item shorter than 2^32 bytes (not checked).  They only enqueue on `stream` (NULL = the context
+ * stream) and allocate nothing; no prepare call; capturable into a HIP graph.  Decrypt is three
+ * launches: the checks that precede the ladder (they also gather R out of the ciphertexts, which the
+ * ladder reads as rows), the ladder of gsv_ecdh_batch_dev, and the symmetric kernel (timed as
+ * GSV_K_ECIES; the first two as GSV_K_ECRECOVER).  Encrypt is three as well: gsv_pubkey_create_batch_dev's
+ * launch for eph G, the ladder, the symmetric kernel.
+ * d_work: gsv_ecies_work_bytes(n, encrypt) bytes of the caller's.  The launches hand each other the
+ * derived keys (and R) there; the symmetric kernel overwrites all of it with zeros before it ends.
+ * d_status is written twice in Decrypt (the early checks, then the final status). */
+size_t gsv_ecies_work_bytes(size_t n, int encrypt);
+int gsv_ecies_decrypt_batch_dev(gsv_ctx *ctx, const uint8_t *d_ct, const uint64_t *d_ct_off,
+                                const uint8_t *d_seckey32, const uint8_t *d_s2, const uint64_t *d_s2_off, size_t n,
+                                uint8_t *d_msg_out, uint32_t *d_msg_len, uint8_t *d_status, uint8_t *d_work,
+                                void *stream);
+int gsv_ecies_encrypt_batch_dev(gsv_ctx *ctx, const uint8_t *d_msg, const uint64_t *d_msg_off,
+                                const uint8_t *d_pub64, const uint8_t *d_eph_seckey32, const uint8_t *d_iv16,
+                                const uint8_t *d_s2, const uint64_t *d_s2_off, size_t n, uint8_t *d_ct_out,
+                                uint8_t *d_status, uint8_t *d_work, void *stream);
 
 /* ---- the ecrecover precompile (core/vm/contracts.go:78-101) ----
  * Input i = in[off[i] .. off[i+1]) = hash(32) || v(32) || r(32) || s(32), right-padded with zeros to
