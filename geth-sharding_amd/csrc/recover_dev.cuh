@@ -330,8 +330,7 @@ GSV_DI bool recover_tail_twisted(fe& qx, fe& qy, const gej9& p1, bool p1inf, con
         fe9_sqr(zz, p2.z);                   // 1
         fe9_mul(z2z2, c, zz);                // Z2^2 = c Z*^2, 1
         fe9_mul(u1, p1.x, z2z2);             // 1
-        fe9_neg<1>(t, u1);
-        fe9_mul_add(h, p2.x, z1z1, t);       // H = U2 - U1, 1 (weakly normalised)
+        fe9_mul_sub(h, p2.x, z1z1, u1);      // H = U2 - U1, 1*1 -> 1 (weakly normalised)
         fe9_mul(s1p, p1.y, p2.z);
         fe9_mul(s1p, s1p, z2z2);             // S1', 1
         fe9_mul(s2, p2.y, p1.z);             // 1*2
@@ -342,8 +341,7 @@ GSV_DI bool recover_tail_twisted(fe& qx, fe& qy, const gej9& p1, bool p1inf, con
         fe9_mul(hhh, h, hh);                 // H^3
         fe9_mul(v, u1, hh);                  // V = U1 H^2
         fe9_mul(cs1, c, s1p);                // c S1'
-        fe9_negsum3<3>(t, hhh, v, v);        // -(H^3 + 2V)
-        fe9_sqr_add(a1, s2, t);              // S2^2 - H^3 - 2V, 1
+        fe9_sqr_sub2<2>(a1, s2, hhh, v);     // S2^2 - H^3 - 2V, 1
         fe9_mul_add(x3a, cs1, s1p, a1);      // X3a = S2^2 + c S1'^2 - H^3 - 2V, 1
         fe9_mul(t, s2, s1p);
         fe9_add(db, t, t);                   // db = 2 S2 S1' = -X3b, 2

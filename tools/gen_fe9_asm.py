@@ -326,6 +326,128 @@ def full_lines3(terms_of_column, addend=False):
     return L
 
 
+# ------------------------------------------------------- column form 3 with subtrahends
+# K p is added so that the value stays non-negative: -K (2^32 + 977) starts limb 0's chain, +K joins
+# T (units of 2^256)
+SUB_K = 8192
+SUB_BIAS0 = -SUB_K * ((1 << 32) + 977)
+
+
+def opnd3s(nsub):
+    """Operand numbering of the subtrahend statements: form 2's, then the subtrahend arrays (9 limbs
+    each), the 64-bit SGPR constant SUB_BIAS0 and the SGPR constant 8 * 31264."""
+    O = {k: v for k, v in OPND2.items() if k not in ("c", "d")}
+    for n in range(nsub):
+        O[f"s{n}"] = 32 + 9 * n
+    O["kbias"] = 32 + 9 * nsub
+    O["k250112"] = 33 + 9 * nsub
+    return O
+
+
+def full_lines3s(terms_of_column, subs):
+    """Form 3 with subtrahends: r = (the product the terms spell) - sum_n k_n s_n, for subs = the list
+    of k_n in {1, 2} (one 9-limb operand array s_n each).  Limb j of s_n enters limb j's chain as ONE
+    v_mad_i64_i32 by the inline constant -k_n, where form 3's addend entered as a multiply-add by 1:
+    nothing is negated or biased limb by limb outside the statement.  The low chains D are then SIGNED
+    64-bit values: their carries are arithmetic shifts (floor division: D = (D & mask) + 2^29 (D >> 29)
+    holds for negative D too), the masks stay, and the unsigned multiply-adds that follow on D are the
+    same additions mod 2^64.  The high columns 9..16 hold products only and stay unsigned.
+
+    Bounds (checked instruction by instruction in tests/test_asm_emulated_signed.py).
+      * Every s_n limb < 2^31 (the addend's precondition: a non-negative i32).
+      * m_a m_b <= 3.5 (squarings: m_a <= 1.87), half of the unsigned forms' 7: a column's products sum
+        to < 31.5 2^58, and with the carry (< 2^35) and the folds (< 2^48) a chain stays below 2^63.
+        (Z3 = (Z1 + H)^2 - Z1^2 - H^2 squares a magnitude-2 operand, whose column 7 reaches 2^63 + 2^56:
+        it keeps the unsigned addend form.)
+      * From below: a chain takes at most 3 (2^31 - 1) off (k_0 + k_1 <= 3) and a carry >= -2^17 (limb
+        0 starts at SUB_BIAS0 > -2^46): every chain > -2^47.
+      * Non-negativity.  The masked limbs are non-negative whatever the chains' signs; what must not be
+        negative is T, the part at and above 2^256, which the final fold multiplies as an unsigned
+        value.  Limb 8's chain is >= -3 (2^31 - 1) - 2^6, so its carry (>> 24) is >= -385, and
+        T = carry + 2^13 o17 + K >= 0 for K = SUB_K = 8192 > 385.  K p = K 2^256 - K (2^32 + 977): the
+        second part is limb 0's start, SUB_BIAS0, read from an SGPR pair in the slot where the unsigned
+        forms start from 0; the first rides in T's multiply-add as (o17 + 1) 2^13, with o17 + 1 =
+        8 hi(P_16) + 1 one v_lshl_add_u32 in place of form 3's shift (limb 8 reads 31264 o17 as
+        hi(P_16) * 250112 instead).  No instruction more than the addend form has per subtrahend.
+      * T < 2^46 + 2^13, as form 3: the output is a product's output (limb 2 < 2^29 + 2^24)."""
+    O = opnd3s(len(subs))
+    opnd = lambda x: f"%{O['a'] + x}" if x < 9 else f"%{O['b'] + x - 9}"
+    r = lambda k: f"%{O['r'] + k}"
+    C, c0, c1 = "v[2:3]", "v2", "v3"
+    D, d0, d1 = "v[4:5]", "v4", "v5"
+    lo = lambda k: "v2" if k == 9 else f"v{6 + 2 * (k - 10)}"
+    hi = lambda k: "v3" if k == 9 else f"v{7 + 2 * (k - 10)}"
+    K31264, K256, K977, SD = f"%{O['k31264']}", f"%{O['k256']}", f"%{O['k977']}", f"%{O['sd']}"
+    K8192, KBIAS, K250112 = f"%{O['k8192']}", f"%{O['kbias']}", f"%{O['k250112']}"
+    L = []
+    for k in range(9, 17):                                 # high columns: form 2's chains, unsigned
+        if k == 9:
+            acc, first = C, True
+        else:
+            acc = PAIR2[k]
+            L.append(f"v_mad_u64_u32 {acc}, {SD}, {hi(k - 1)}, 8, 0")
+            first = False
+        for (x, y) in terms_of_column(k):
+            assert x < 18 and y < 18
+            L.append(f"v_mad_u64_u32 {acc}, {SD}, {opnd(x)}, {opnd(y)}, {'0' if first else acc}")
+            first = False
+    L.append(f"v_lshl_add_u32 {c1}, {hi(16)}, 3, 1")       # o17 + 1 = 8 hi(P_16) + 1 <= 2^32 - 7
+    for j in range(9):                                     # low limbs: signed chains
+        for n, k in enumerate(subs):
+            start = KBIAS if (j == 0 and n == 0) else D
+            L.append(f"v_mad_i64_i32 {D}, {SD}, %{O[f's{n}'] + j}, -{k}, {start}")
+        for (x, y) in terms_of_column(j):
+            L.append(f"v_mad_u64_u32 {D}, {SD}, {opnd(x)}, {opnd(y)}, {D}")
+        if j < 8:
+            L.append(f"v_mad_u64_u32 {D}, {SD}, {lo(j + 9)}, {K31264}, {D}")
+            if j:
+                L.append(f"v_mad_u64_u32 {D}, {SD}, {lo(j + 8)}, {K256}, {D}")
+            L.append(f"v_and_b32_e32 {r(j)}, 0x1fffffff, {d0}")
+            L.append(f"v_ashrrev_i64 {D}, 29, {D}")
+        else:
+            L.append(f"v_mad_u64_u32 {D}, {SD}, {hi(16)}, {K250112}, {D}")  # 31264 o17
+            L.append(f"v_mad_u64_u32 {D}, {SD}, {lo(16)}, {K256}, {D}")
+            L.append(f"v_and_b32_e32 {r(8)}, 0xffffff, {d0}")
+            L.append(f"v_ashrrev_i64 {D}, 24, {D}")
+    T, t0, t1 = "v[6:7]", "v6", "v7"                      # P_10 is dead by now
+    L.append(f"v_mad_u64_u32 {T}, {SD}, {c1}, {K8192}, {D}")  # T = (c >> 24) + (o17 + 1) 2^13 >= 0
+    L.append(f"v_mov_b32 {d1}, 0")
+    L.append(f"v_mov_b32 {d0}, {r(0)}")
+    L.append(f"v_mad_u64_u32 {D}, {SD}, {t0}, {K977}, {D}")
+    L.append(f"v_mad_u32_u24 {d1}, {t1}, {K977}, {d1}")
+    L.append(f"v_and_b32_e32 {r(0)}, 0x1fffffff, {d0}")
+    L.append(f"v_lshrrev_b64 {D}, 29, {D}")
+    L.append(f"v_lshl_add_u64 {D}, {T}, 3, {D}")
+    L.append(f"v_mad_u64_u32 {D}, {SD}, {r(1)}, 1, {D}")
+    L.append(f"v_and_b32_e32 {r(1)}, 0x1fffffff, {d0}")
+    L.append(f"v_alignbit_b32 {t0}, {d1}, {d0}, 29")
+    L.append(f"v_add_u32 {r(2)}, {r(2)}, {t0}")
+    return L
+
+
+def full3s(name, doc, terms_of_column, subs):
+    L = full_lines3s(terms_of_column, subs)
+    sub_names = ["c", "d"][:len(subs)]
+    outs = ", ".join([f'"=&v"(r[{i}])' for i in range(9)] + ['"=&s"(sd)'])
+    ins = ", ".join([f'"v"(a[{i}])' for i in range(9)] + [f'"v"(b[{j}])' for j in range(9)] +
+                    ['"s"(k31264)', '"s"(k256)', '"s"(k977)', '"s"(k8192)'] +
+                    [f'"v"({s}[{j}])' for s in sub_names for j in range(9)] +
+                    ['"s"(kbias)', '"s"(k250112)'])
+    body = "\\n\\t".join(L)
+    clob = ", ".join(f'"v{i}"' for i in range(2, 20))
+    return [f"// {doc}",
+            f"__device__ __forceinline__ void {name}(uint32_t r[9], const uint32_t a[9], const uint32_t b[9]"
+            + "".join(f", const uint32_t {s}[9]" for s in sub_names) + ") {",
+            "    uint64_t sd;",
+            "    uint32_t k31264 = 31264u, k256 = 256u, k977 = 977u, k8192 = 8192u, k250112 = 250112u;",
+            f"    int64_t kbias = {SUB_BIAS0}ll;  // -{SUB_K} (2^32 + 977)",
+            f'    asm("{body}"',
+            f"        : {outs}",
+            f"        : {ins}",
+            f"        : {clob});",
+            "}"]
+
+
 def full2(name, doc, terms_of_column, addend=False, dot=False, gen=None, third=False):
     """third: a third operand array c that the terms read (no addend, no d)"""
     L = (gen or full_lines2)(terms_of_column, addend)
@@ -354,6 +476,7 @@ def main():
            "// (full_lines3).  Forms 1 (every column masked and shifted) and 2 (high columns 9..16 unmasked in",
            "// fixed register pairs) stay in the generator as the instruction emulator's references",
            "// (tests/test_asm_emulated.py); the kernels use form 3 only (r04: 175 -> 136 instructions a product).",
+           "// The *_sub* statements are form 3 with subtrahends in signed low chains (full_lines3s).",
            "#pragma once", "#include <stdint.h>",
            "namespace gsv {"]
     specs = [("fe9_mul_full", "r = a * b mod p, weakly normalised (fe9_mul's contract)", MUL_TERMS, False, False),
@@ -368,6 +491,16 @@ def main():
               SQR3_TERMS, False, "third")]
     for name, doc, terms, add, dot in specs:
         out += full2(name, doc, terms, add, dot is True, gen=full_lines3, third=dot == "third")
+    sub_specs = [("fe9_mul_sub_full", "r = a * b - c mod p, c limbs < 2^31, m_a m_b <= 3.5 (fe9_mul_sub's contract)",
+                  MUL_TERMS, [1]),
+                 ("fe9_sqr_sub2_k1_full", "r = a^2 - c - d mod p with b = 2a limb-wise (fe9_sqr_sub2<1>'s contract)",
+                  SQR_TERMS, [1, 1]),
+                 ("fe9_sqr_sub2_k2_full", "r = a^2 - c - 2 d mod p with b = 2a limb-wise (fe9_sqr_sub2<2>'s contract)",
+                  SQR_TERMS, [1, 2]),
+                 ("fe9_sqr_sub1_k2_full", "r = a^2 - 2 c mod p with b = 2a limb-wise (fe9_sqr_sub2<2> without c)",
+                  SQR_TERMS, [2])]
+    for name, doc, terms, subs in sub_specs:
+        out += full3s(name, doc, terms, subs)
     out.append("}  // namespace gsv")
     with open(OUT, "w") as f:
         f.write("\n".join(out) + "\n")
