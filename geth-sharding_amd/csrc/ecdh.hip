@@ -11,7 +11,7 @@
 // The divergence: a point that is not on the curve is refused (GSV_ST_INVALID_CURVE), where the reference
 // returns the output of its addition formulas on another curve (include/gsv.h says why).
 //
-// Algorithm: the curve check (canonical compare, as pubkey_parse9 does it), recover_dev.cuh's GLV w = 4
+// Algorithm: the curve check (canonical compare, secp256k1_point.cuh on_curve9), secp256k1_glv.cuh's GLV w = 4
 // ladder (glv_mul_point: a uniform schedule of odd signed digits, no skipped adds) on the caller's
 // point, one CONSTANT-TIME safegcd inversion mod p for the affine result (Z depends on the secret
 // scalar: the variable-time inversion's trip count would show in the wave's time), a full normalise
@@ -20,7 +20,9 @@
 // harmless inputs (the generator, k = 1) and has its outputs zeroed at the end: no lane leaves the
 // ladder early.
 #include "opcount.cuh"
-#include "recover_dev.cuh"
+#include "gsv_internal.h"
+#include "secp256k1_glv.cuh"  // before the other secp256k1 headers
+#include "secp256k1_point.cuh"
 #include "ecies_kdf.cuh"
 
 namespace gsv {
@@ -49,62 +51,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GSV_ECR_WAV
         fe9_normalize_full(py);
     }
     // scalar_set_b32's overflow and scalar_is_zero: the reference's only failure
-    const bool scalar_ok = limbs_lt(k.v, SN) && !sc_is_zero(k);
-    bool curve_ok;
-    {
-        fe9 t, c, yy;
-        fe9_sqr(t, px);
-        fe9_mul(c, t, px);
-        c.v[0] += 7u;                        // x^3 + 7, limb 0 < 2^29 + 7
-        fe9_normalize_full(c);
-        fe9_sqr(yy, py);
-        fe9_normalize_full(yy);
-        curve_ok = fe9_eq_canon(yy, c);
-    }
+    const bool scalar_ok = seckey_ok(k);
+    const bool curve_ok = on_curve9(px, py);
     const bool ok = scalar_ok && curve_ok;
-    {
-        // an invalid item runs as 1 * G
-        fe9 gx, gy;
-        fe9_from_const(gx, GX);
-        fe9_from_const(gy, GY);
-        fe9_cmov(px, gx, !ok);
-        fe9_cmov(py, gy, !ok);
+    // an invalid item runs as 1 * G
+    ge9_set_g_unless(px, py, ok);
+    // (sc_set_one_unless, written out: the call changes this kernel's instruction schedule)
 #pragma unroll
-        for (int j = 0; j < 8; j++) k.v[j] = ok ? k.v[j] : (j == 0 ? 1u : 0u);
-    }
+    for (int j = 0; j < 8; j++) k.v[j] = ok ? k.v[j] : (j == 0 ? 1u : 0u);
 
     gej9 acc;  // k P: k in [1, n) and P of order n, so the flag stays clear; honoured all the same
     bool ainf;
     glv_mul_point(acc, ainf, k, px, py, GSV_LTAB_LANE);
     const bool good = ok && !ainf;
 
-    // affine: Z^-1 by the constant-time divsteps
-    fe9 zi, zi2, x;
-    {
-        fe9 z = acc.z;
-        fe9_normalize_full(z);
-        uint32_t zw[8], iw[8];
-        fe9_to_words(zw, z);
-        modinv30_words_ct(iw, zw, MI30_P);
-        fe9_from_words(zi, iw);
-    }
-    fe9_sqr(zi2, zi);
-    fe9_mul(x, acc.x, zi2);
-    fe9_normalize_full(x);
+    // affine by the constant-time inversion: Z depends on the secret scalar
+    fe9 zi, zi2;
+    fe xa;
+    gej9_affine_x_ct(xa, zi, zi2, acc);
     uint32_t xo[8];
-    fe9_to_words(xo, x);
 #pragma unroll
-    for (int j = 0; j < 8; j++) xo[j] = good ? xo[j] : 0u;
+    for (int j = 0; j < 8; j++) xo[j] = good ? xa.v[j] : 0u;
 
     if (xy64) {  // wave-uniform: ScalarMult's Y
-        fe9 zi3, y;
-        fe9_mul(zi3, zi2, zi);
-        fe9_mul(y, acc.y, zi3);
-        fe9_normalize_full(y);
+        fe ya;
+        gej9_affine_y_ct(ya, acc, zi, zi2);
         uint32_t yo[8];
-        fe9_to_words(yo, y);
 #pragma unroll
-        for (int j = 0; j < 8; j++) yo[j] = good ? yo[j] : 0u;
+        for (int j = 0; j < 8; j++) yo[j] = good ? ya.v[j] : 0u;
         limbs_to_be(xy64 + (size_t)i * 64, xo);
         limbs_to_be(xy64 + (size_t)i * 64 + 32, yo);
     }

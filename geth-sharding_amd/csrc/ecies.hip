@@ -15,7 +15,10 @@
 //   Encrypt   keys48[48 n] | R as 04 || X || Y [65 n] | the ladder's status [n] | k_pubkey_create's [n]
 // and the last kernel of a call overwrites its item's part of every region with zeros.
 #include "opcount.cuh"
-#include "recover_dev.cuh"
+#include "gsv_internal.h"
+#include "secp256k1_scalar.cuh"
+#include "secp256k1_fe9.cuh"
+#include "secp256k1_point.cuh"
 #include "ecies_sym_dev.cuh"
 
 namespace gsv {
@@ -63,23 +66,15 @@ __global__ __launch_bounds__(256) void k_ecies_parse(const uint8_t* __restrict__
     // 5. a coordinate >= p is refused (the strict reading of elliptic.Unmarshal)
     if (st == GSV_ST_OK && !(limbs_lt(xw, FP) && limbs_lt(yw, FP))) st = GSV_ST_INVALID_PUBKEY;
     // 6. IsOnCurve (ecies.go:337), as k_ecdh tests it
-    bool curve_ok;
-    {
-        fe9 px, py, t, cc, yy;
-        fe9_from_words(px, xw);
-        fe9_from_words(py, yw);
-        fe9_normalize_full(px);
-        fe9_normalize_full(py);
-        fe9_sqr(t, px);
-        fe9_mul(cc, t, px);
-        cc.v[0] += 7u;
-        fe9_normalize_full(cc);
-        fe9_sqr(yy, py);
-        fe9_normalize_full(yy);
-        curve_ok = fe9_eq_canon(yy, cc);
-    }
+    fe9 px, py;
+    fe9_from_words(px, xw);
+    fe9_from_words(py, yw);
+    fe9_normalize_full(px);
+    fe9_normalize_full(py);
+    const bool curve_ok = on_curve9(px, py);  // every lane computes it
     if (st == GSV_ST_OK && !curve_ok) st = GSV_ST_INVALID_CURVE;
-    // 7. the secret key in [1, n)
+    // 7. the secret key in [1, n) (seckey_ok's verdict; its OR-reduction in place of this chain of
+    // compares changes the kernel's instructions, so the chain stays)
     bool kzero = true;
 #pragma unroll
     for (int j = 0; j < 8; j++) kzero = kzero && k[j] == 0u;

@@ -12,7 +12,7 @@
 // Algorithm (ours, MI355X-first — not libsecp256k1's Strauss-wNAF, which branches per digit and
 // wastes SIMD lanes).  Field arithmetic: 9 x 29-bit limbs with lazy reduction (secp256k1_fe9.cuh).
 //   * u2*R: GLV split u2 = k1 + k2*lambda (|k1|,|k2| < 2^128), fixed-schedule odd-digit w = 4
-//     recoding (recover_dev.cuh GSV_GLV_W: an add every 4th bit, identical across the wave: no
+//     recoding (secp256k1_glv.cuh GLV_W: an add every 4th bit, identical across the wave: no
 //     divergence), 8-entry table {1,3,...,15}R (entries 0..3 in LDS, 4..7 in per-lane scratch: the
 //     LDS of two waves per SIMD holds four), built on an isomorphic curve
 //     (libsecp-style "global z") so all table points are affine without an inversion; the lambda
@@ -26,10 +26,11 @@
 //     (gsv_internal.h COMB_BITS; 16-bit windows from the Infinity Cache were 1.3 % slower).
 //   * no square root up front: u2*R runs on the curve y^2 = x^3 + 7 c^3 (c = x^3 + 7) where R is
 //     (c x, c^2); one general add to combine, carried as a + t b (t = y_R); one exponentiation by
-//     (p-3)/4 then gives both y_R and Z^-1 (recover_dev.cuh GSV_RECOVER_TWIST); fused Keccak-256
+//     (p-3)/4 then gives both y_R and Z^-1 (recover_dev.cuh recover_tail_twisted); fused Keccak-256
 //     address.
 #include "opcount.cuh"
-#include "recover_dev.cuh"
+#include "recover_dev.cuh"  // before the other secp256k1 headers (secp256k1_glv.cuh)
+#include "secp256k1_sign.cuh"
 
 namespace gsv {
 
@@ -134,7 +135,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GSV_ECR_WAV
 }
 
 // Fixed-base comb table: entry (w, d) = d * 2^(COMB_BITS w) * G, affine, canonical fe9 limbs
-// (x[9] y[9] + 2 pad words, recover_dev.cuh gtab_load).  Built once per context in two launches:
+// (x[9] y[9] + 2 pad words, secp256k1_comb.cuh gtab_load).  Built once per context in two launches:
 // k_gtable_base writes each window's base B_w = 2^(COMB_BITS w) G into its unused d = 0 slot, then
 // k_gtable_init computes d * B_w (COMB_BITS-bit double-and-add) for every d >= 1.
 GSV_DI void gtab_store(uint4* e, const gej9& acc) {

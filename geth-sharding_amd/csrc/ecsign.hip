@@ -14,25 +14,16 @@
 //
 // Algorithm: the nonce of rfc6979_dev.cuh (16 SHA-256 compressions at counter 0; a retry starts the
 // generator again, as the reference does, so that none of its state occupies registers through the curve
-// arithmetic), then recover_dev.cuh's ecdsa_sign_core: one 20-bit comb
+// arithmetic), then secp256k1_sign.cuh's ecdsa_sign_core: one 20-bit comb
 // multiplication over the context's G table, one inversion mod p for the affine R, the constant-time
 // safegcd inversion of the nonce mod n.  No GLV ladder, so no LDS table.  An item with an invalid key
 // runs the whole schedule on the key 1 and has its output zeroed at the end: no lane leaves early.
 #include "opcount.cuh"
-#include "recover_dev.cuh"
+#include "secp256k1_comb.cuh"
+#include "secp256k1_sign.cuh"
 #include "rfc6979_dev.cuh"
 
 namespace gsv {
-
-// secp256k1_ec_seckey_verify: 0 < d < n
-GSV_DI bool seckey_ok(const sc& d) { return limbs_lt(d.v, SN) && !sc_is_zero(d); }
-
-GSV_DI bool limbs_zero(const uint32_t v[8]) {
-    uint32_t o = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) o |= v[i];
-    return o == 0;
-}
 
 // compiled for two waves per SIMD (256 registers), as k_synth_sign comes out on its own
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GSV_ECR_WAVES, GSV_ECR_WAVES))) void k_ecsign(
@@ -45,8 +36,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GSV_ECR_WAV
     load32_be(d.v, seckey32 + (size_t)i * 32);
     load32_be(m, msg32 + (size_t)i * 32);
     const bool keyok = seckey_ok(d);
-#pragma unroll
-    for (int j = 0; j < 8; j++) d.v[j] = keyok ? d.v[j] : (j == 0 ? 1u : 0u);
+    sc_set_one_unless(d, keyok);
     uint32_t r[8], s[8], recid, counter = 0;
     bool done;
 #pragma unroll 1
@@ -66,8 +56,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GSV_ECR_WAV
         }
         // a nonce of 0 or >= n is passed over (2^-128): the lane signs with 1 and discards the result
         const bool kok = seckey_ok(k);
-#pragma unroll
-        for (int j = 0; j < 8; j++) k.v[j] = kok ? k.v[j] : (j == 0 ? 1u : 0u);
+        sc_set_one_unless(k, kok);
         ecdsa_sign_core(r, s, recid, d, k, m, gtab);
         done = kok && !limbs_zero(r) && !limbs_zero(s);
         counter++;
@@ -93,8 +82,7 @@ __global__ __launch_bounds__(256) void k_pubkey_create(const uint8_t* __restrict
     sc d;
     load32_be(d.v, seckey32 + (size_t)i * 32);
     const bool keyok = seckey_ok(d);
-#pragma unroll
-    for (int j = 0; j < 8; j++) d.v[j] = keyok ? d.v[j] : (j == 0 ? 1u : 0u);
+    sc_set_one_unless(d, keyok);
     gej9 P;
     bool pinf;  // d in [1, n): never the identity
     comb_mul_g9(P, pinf, d, gtab);

@@ -11,7 +11,7 @@
 //   libsecp256k1/src/ecdsa_impl.h ecdsa_sig_verify: r, s != 0; X = (m/s) G + (r/s) P; X != O;
 //                         r Z^2 == X_x or (r < p - n and (r + n) Z^2 == X_x), both projective
 //
-// Algorithm: the recovery kernels' parts (recover_dev.cuh) on a caller-chosen point.  u2 P is the GLV
+// Algorithm: the recovery kernels' parts (secp256k1_glv.cuh, secp256k1_comb.cuh) on a caller-chosen point.  u2 P is the GLV
 // w = 4 ladder (glv_mul_point) on the parsed key, u1 G the 20-bit comb; one general Jacobian add that
 // produces X3 and Z3 only, then the projective comparison.  No square root for an uncompressed key,
 // no inversion mod p anywhere in k_ecverify: recovery's exponentiation by (p - 3) / 4 has no
@@ -19,7 +19,9 @@
 // An invalid item runs the whole schedule on harmless inputs (the generator, r = s = 1) and has its
 // verdict forced to 0 at the end: no lane leaves the ladder early.
 #include "opcount.cuh"
-#include "recover_dev.cuh"
+#include "secp256k1_glv.cuh"  // before the other secp256k1 headers
+#include "secp256k1_comb.cuh"
+#include "secp256k1_point.cuh"
 
 namespace gsv {
 
@@ -37,10 +39,8 @@ GSV_DI bool pubkey_parse9(fe9& x, fe9& y, const uint8_t* __restrict__ row, uint3
     bool ok = (comp || full) && limbs_lt(xw, FP);
     fe9_from_words(x, xw);
     fe9_from_words(y, yw);
-    fe9 c, t;
-    fe9_sqr(t, x);
-    fe9_mul(c, t, x);
-    c.v[0] += 7u;                            // x^3 + 7, limb 0 < 2^29 + 7
+    fe9 c;
+    curve_rhs9(c, x);                        // x^3 + 7, shared by the root and the curve test
     if (FE9_ANY(comp)) {                     // wave-uniform: no lane pays the root for a 65-byte key
         fe9 root;
         bool sq = fe9_sqrt(root, c);
@@ -63,11 +63,7 @@ GSV_DI bool pubkey_parse9(fe9& x, fe9& y, const uint8_t* __restrict__ row, uint3
         bool par = prefix == 4u || (yw[0] & 1u) == (prefix & 1u);
         ok = ok && (!full || (limbs_lt(yw, FP) && on && par));
     }
-    fe9 gx, gy;
-    fe9_from_const(gx, GX);
-    fe9_from_const(gy, GY);
-    fe9_cmov(x, gx, !ok);
-    fe9_cmov(y, gy, !ok);
+    ge9_set_g_unless(x, y, ok);
     return ok;
 }
 
@@ -135,11 +131,8 @@ GSV_DI bool verify_core(const uint32_t msg[8], const uint32_t r[8], const uint32
     const bool sigok = limbs_lt(r, SN) && limbs_lt(s, SN) && !sc_is_zero(rs) && !sc_is_zero(ss) &&
                        !sc_is_high(ss);
     // an invalid signature runs as r = s = 1
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        rs.v[i] = sigok ? rs.v[i] : (i == 0 ? 1u : 0u);
-        ss.v[i] = sigok ? ss.v[i] : (i == 0 ? 1u : 0u);
-    }
+    sc_set_one_unless(rs, sigok);
+    sc_set_one_unless(ss, sigok);
     sc_cond_sub_n(m.v, msg, 0);  // msg mod n (msg < 2^256 < 2n); may be 0
 
     // u1 = m / s, u2 = r / s

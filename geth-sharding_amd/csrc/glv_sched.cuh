@@ -1,4 +1,4 @@
-// The integer-only pieces of the secp256k1 recovery's scalar schedule (recover_dev.cuh binds them to
+// The integer-only pieces of the secp256k1 recovery's scalar schedule (secp256k1_glv.cuh binds them to
 // its constants): the GLV ladder's digits read from the scalar's bits, and the split's two short
 // products.  Plain C++ when __HIPCC__ is not defined, so tests/native/recover_trim_host.cpp runs the
 // same text on the CPU (there the 4 x 4 product is a loop instead of mul_asm.cuh's statement).
@@ -6,6 +6,8 @@
 #include <stdint.h>
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#include "mul_asm.cuh"  // mul_4x4_fx
 #define GLV_FN __device__ __forceinline__
 #else
 #define GLV_FN static inline

@@ -167,7 +167,7 @@ constexpr int COMB_BITS = 20;
 constexpr int COMB_WINDOWS = (256 + COMB_BITS - 1) / COMB_BITS;  // the top window may be partial
 static_assert(COMB_BITS >= 4 && COMB_BITS <= 26, "comb window width");
 constexpr size_t GTAB_ENTRIES = (size_t)COMB_WINDOWS << COMB_BITS;
-constexpr size_t GTAB_ENTRY_BYTES = 80;  // fe9 x[9] y[9] + 2 pad words (recover_dev.cuh gtab_load)
+constexpr size_t GTAB_ENTRY_BYTES = 80;  // fe9 x[9] y[9] + 2 pad words (secp256k1_comb.cuh gtab_load)
 constexpr size_t GTAB_BYTES = GTAB_ENTRIES * GTAB_ENTRY_BYTES;
 
 }  // namespace gsv

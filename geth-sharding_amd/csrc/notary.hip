@@ -20,7 +20,8 @@
 // restated for one lane: the blob's bytes are read through the chunk map (byte k at chunk k/31, offset
 // 1 + k%31).
 #include "opcount.cuh"
-#include "recover_dev.cuh"
+#include "recover_dev.cuh"  // before the other secp256k1 headers (secp256k1_glv.cuh)
+#include "secp256k1_sign.cuh"
 
 namespace gsv {
 

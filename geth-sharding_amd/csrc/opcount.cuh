@@ -6,10 +6,10 @@
 
 namespace gsv {
 enum OpKind : int {
-    OPC_FE_MUL = 0,  // secp256k1 field product (fe9 / 8x32)
+    OPC_FE_MUL = 0,  // secp256k1 field product (fe9)
     OPC_FE_SQR = 1,  // secp256k1 field squaring
     OPC_SC_MUL = 2,  // scalar (mod n) product, incl. the GLV split's 256x256 products
-    OPC_SC_SQR = 3,
+    OPC_SC_SQR = 3,  // retired (the scalar squaring left with sc_inv): the slot stays, readers index by position
     OPC_BN_MUL = 4,  // BN254 F_p Montgomery product
     OPC_MODINV = 5,  // safegcd inversion (mod p, mod n, BN254 p)
     OPC_BN_REDC = 6, // BN254 Montgomery reduction (one per fq_mul / fq_mul2 / fq_dot)

@@ -74,7 +74,7 @@ SHA_FN void sha256_compress_inline(uint32_t (&s)[8], uint32_t (&w)[16]) {
 // copies are ~190 KB of straight-line code (three times the instruction cache), and the round constants
 // the compiler then keeps in scalar registers across them, with the values it spills for it, cost the
 // signing kernel its second wave per SIMD.  State and block travel in VGPR vectors (an aggregate or
-// pointer argument would pin them to scratch memory), as gej9_dbl_ool's point does (recover_dev.cuh).
+// pointer argument would pin them to scratch memory), as gej9_dbl_ool's point does (secp256k1_glv.cuh).
 typedef uint32_t sha_v8 __attribute__((ext_vector_type(8)));
 typedef uint32_t sha_v16 __attribute__((ext_vector_type(16)));
 static __device__ __noinline__ sha_v8 sha256_compress_ool(sha_v8 sv, sha_v16 wv) {

@@ -549,7 +549,7 @@ int oracle_secp_sign(uint8_t sig65[65], const uint8_t msg32[32], const uint8_t s
     return 1;
 }
 
-/* The GPU's synthetic signer (gsv_synth_sign, recover_dev.cuh derive32 / ecdsa_sign) restated for
+/* The GPU's synthetic signer (gsv_synth_sign, secp256k1_sign.cuh derive32 / ecdsa_sign) restated for
  * the configs[1] fixture: msg, key, nonce = Keccak256(le64(seed) || le64(i) || "msg"/"key"/"nce") as
  * big-endian numbers, key and nonce reduced mod n (0 -> 1), low-s signature with its recid. */
 static void synth_derive(uint8_t out[32], uint64_t seed, uint64_t i, const char *tag) {

@@ -1,6 +1,7 @@
-"""The scalar schedule of the secp256k1 recovery (geth-sharding_amd/csrc/recover_dev.cuh) restated in
-Python integers: sc_mul_shift272, sc_split_lambda, glv_make_odd, the sign handling, recode_glv, the
-GLV ladder's add order and the fixed-base comb's window digits.
+"""The scalar schedule of the secp256k1 recovery (geth-sharding_amd/csrc/secp256k1_glv.cuh and
+secp256k1_comb.cuh, with the constants of secp256k1_dev.cuh) restated in Python integers:
+sc_mul_shift272, sc_split_lambda, glv_make_odd, the sign handling, recode_glv, the GLV ladder's add
+order and the fixed-base comb's window digits.
 
 Every constant and window width is read from the source text of the device headers, so a change there
 flows into the model (or fails the parse); nothing is retyped here.  The model follows the device's

@@ -209,7 +209,7 @@ def test_conversion_back(lib):
 
 def test_ladder_step_and_why_the_window_is_even(lib):
     """four doublings and an add are 16 P + q; an ODD run before the add leaves the sum at
-    -2^n P + q (GLV_W must be even: recover_dev.cuh asserts it)"""
+    -2^n P + q (GLV_W must be even: secp256k1_glv.cuh asserts it)"""
     rng = random.Random(9)
     r, s = U27(), U27()
     for it in range(10):

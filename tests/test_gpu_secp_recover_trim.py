@@ -1,6 +1,6 @@
 """GPU parity of the recovery's prologue, the starts of its two sums and its exceptional-case filter
-(recover_dev.cuh: digits read from the scalar's bits, the affine + affine first adds, the comb's adds
-without a test, the one-limb filter, the split's short products), on crafted signatures (r = x_R,
+(secp256k1_glv.cuh, secp256k1_comb.cuh: digits read from the scalar's bits, the affine + affine first
+adds, the comb's adds without a test, the one-limb filter, the split's short products), on crafted signatures (r = x_R,
 s = u2 r, msg = -u1 r: tests/secp_glv_model.py craft) through the four kernels that inline recover_core,
 at batch sizes 1, 63, 64, 65 and 257 (a lone lane, a ragged wave, a full one, a second wave, a second
 block), bit-exact against the oracle, the doubling case also against Python integers.

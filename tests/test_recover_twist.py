@@ -1,4 +1,4 @@
-"""The twisted-curve recovery tail of csrc/recover_dev.cuh (GSV_RECOVER_TWIST, recover_tail_twisted),
+"""The twisted-curve recovery tail of csrc/recover_dev.cuh (recover_tail_twisted),
 restated with Python integers and checked against affine arithmetic on secp256k1: u2 R computed on
 E_t: y^2 = x^3 + 7 c^3 from R* = (c x, c^2) (no square root), the sum with u1 G carried as a + t b with
 t = y_R, and one exponentiation w = (c z^4)^((p-3)/4) giving both the root and the inverse of Z.

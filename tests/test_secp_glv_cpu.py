@@ -1,8 +1,8 @@
 """CPU tests of the secp256k1 recovery's scalar schedule (tests/secp_glv_model.py: the split, the
-lattice-vector step, the odd-digit recoding and the ladder order of recover_dev.cuh in Python integers)
+lattice-vector step, the odd-digit recoding and the ladder order of secp256k1_glv.cuh in Python integers)
 and of the oracle's chain checker that the GPU sweep of the comb table relies on.  No GPU.
 
-The bounds asserted here are the ones recover_dev.cuh states in comments and relies on: both GLV halves
+The bounds asserted here are the ones secp256k1_glv.cuh states in comments and relies on: both GLV halves
 odd and below 2^130 (GLV_DIGITS windows of GLV_W bits), every digit odd within the 2^(GLV_W-1)-entry
 table, the top digit included (recode_glv takes it unsigned: above 2^GLV_W - 1 it would run into the
 sign bit of the digit code)."""
