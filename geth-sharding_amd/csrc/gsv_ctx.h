@@ -2,6 +2,7 @@
 //   gsv_ctx.hip      context, streams, kernel timing, staging arena, the cache of prepared shapes
 //   gsv_batch.hip    stateless batches: Keccak, ecrecover and its precompile, bn256 add / mul, senders
 //   gsv_ecies.hip    ecies.Encrypt / Decrypt: the launch chains around the ladder
+//   gsv_txsign.hip   types.SignTx: the launch chain around the signature kernel
 //   gsv_trie.hip     chunk root, DeriveSha, Proof of Custody, collation headers
 //   gsv_pairing.hip  BN254 pairing check
 //   gsv_notary.hip   notary validation, shard partition + RCCL all-gather
@@ -187,8 +188,8 @@ struct gsv_ctx {
     struct Pending { int kid; hipEvent_t a, b; };
     std::vector<Pending> pending;
     std::vector<hipEvent_t> free_events;
-    double total_ms[GSV_K_END] = {0};
-    long launches[GSV_K_END] = {0};
+    double total_ms[GSV_K_LIMIT] = {0};
+    long launches[GSV_K_LIMIT] = {0};
     std::mutex tmu;
     std::vector<hipEvent_t> open_ev;  // timer events opened by launch hooks
     hipStream_t cur_stream = nullptr;  // stream of the shape run in progress (launch hooks)

@@ -31,6 +31,32 @@ hipError_t launch_ecsign(const uint8_t* msg32, const uint8_t* seckey32, uint32_t
 hipError_t launch_pubkey_create(const uint8_t* seckey32, uint32_t n, const uint4* gtab, uint8_t* pub65,
                                 uint8_t* addr20, uint8_t* status, hipStream_t st);
 
+// txsign.hip: the two kernels of types.SignTx around launch_ecsign.  What they need of the signer and the
+// chain id is prepared on the host (gsv_txsign.hip) and passed by value:
+//   TxSignSuffix  what the signer's Hash appends to the six fields: rlp(chainId) 80 80 for EIP-155 (at
+//                 most 68 bytes), nothing for Homestead / Frontier.  Word 0 is zero, byte j of the suffix
+//                 is byte 4 + j of w, zero behind it (tx_flat.cuh TxStream's tail layout).
+//   TxSignVTable  the RLP item of V for recovery id 0..3 (row r: TXS_V_WORDS zero-padded words, len[r]
+//                 bytes, at most 67).
+// rec: a uint4 per item {segment offset, segment length, recipient patch offset, status}.
+constexpr uint32_t TXS_SUFFIX_WORDS = 20, TXS_V_WORDS = 17;
+struct TxSignSuffix {
+    uint32_t w[TXS_SUFFIX_WORDS];
+    uint32_t len;
+};
+struct TxSignVTable {
+    uint32_t w[4 * TXS_V_WORDS];
+    uint32_t len[4];
+};
+// the caller's work area of the _dev form (gsv_tx_sign_work_bytes), no padding between its parts:
+// rec 16 n | msg32 32 n | sig65 65 n | sign status n
+constexpr size_t TXS_WORK_PER = 16 + 32 + 65 + 1;
+hipError_t launch_tx_sighash(const uint8_t* d_rlp, const uint64_t* d_off, uint32_t n, const TxSignSuffix& sfx,
+                             uint32_t* d_rec, uint32_t* d_msg32, hipStream_t st);
+hipError_t launch_tx_seal(const uint8_t* d_rlp, const uint64_t* d_off, uint32_t n, const TxSignVTable& vt,
+                          uint64_t growth, const uint32_t* d_rec, const uint8_t* d_sig65, const uint8_t* d_sign_st,
+                          uint8_t* d_out, uint32_t* d_out_len, uint8_t* d_hash32, uint8_t* d_status, hipStream_t st);
+
 // ecdh.hip: secp256k1_ext_scalar_mul and what ECIES derives from its X.  Outputs that are null are not
 // written: xy64 (X || Y), x32 (X), keys48 (Ke || Km); status GSV_ST_OK / GSV_ST_INVALID_KEY /
 // GSV_ST_INVALID_CURVE

@@ -74,6 +74,18 @@ struct PubkeyCreateStage {
     PubkeyCreateStage(Layout& L, size_t n, bool want_addr)
         : key(L.buf(n * 32)), pub(L.buf(n * 65)), addr(L.buf(n * 20, want_addr)), st(L.buf(n)) {}
 };
+// gsv_tx_sign_batch.  The secret keys come FIRST, as in SignStage.  `work` is work_per bytes per item
+// (gsv_tx_sign_work_bytes); `out` holds the slots: the input's bytes plus `growth` per item.
+struct TxSignStage {
+    B8 key, work, rlp;
+    Buf<uint64_t> off;
+    B8 out;
+    Buf<uint32_t> olen;
+    B8 hash, st;
+    TxSignStage(Layout& L, size_t n, size_t work_per, size_t bytes, size_t growth, bool want_hash)
+        : key(L.buf(n * 32)), work(L.buf(n * work_per)), rlp(L.buf(bytes + 8)), off(L.buf<uint64_t>((n + 1) * 8)),
+          out(L.buf(bytes + n * growth)), olen(L.buf<uint32_t>(n * 4)), hash(L.buf(n * 32, want_hash)), st(L.buf(n)) {}
+};
 // gsv_secp256k1_scalar_mul_batch, gsv_ecdh_batch.  Every secret region comes FIRST and contiguous: the
 // scalars, then the secret outputs (the product point; the shared X and the derived keys, each only
 // when asked for).  `secret` is the end of the last of them: the host form overwrites [0, secret) of

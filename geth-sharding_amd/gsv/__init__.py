@@ -780,6 +780,64 @@ def _pubkey_create_batch_dev(self, key_t, pub_t, addr_t, st_t, stream=None):
                                                   _tptr(addr_t) if addr_t is not None else None, _tptr(st_t), sp))
 
 
+def _check_signer(chain_id: int, signer_kind: int) -> bytes:
+    if signer_kind not in (_lib.SIGNER_EIP155, _lib.SIGNER_HOMESTEAD, _lib.SIGNER_FRONTIER):
+        raise ValueError("signer_kind is one of SIGNER_EIP155, SIGNER_HOMESTEAD, SIGNER_FRONTIER")
+    cid = _be(int(chain_id))
+    if chain_id < 0 or len(cid) > 64:
+        raise ValueError("the chain id is a non-negative integer of at most 64 bytes")
+    return cid
+
+
+def _tx_sign_batch(self, txs, keys, chain_id: int, signer_kind: int, want_hash=True):
+    """types.SignTx over a batch (gsv.h gsv_tx_sign_batch): txs = RLP-encoded transactions, signed or not,
+    keys (n,32) uint8 big-endian secret keys.  Returns (signed: list of bytes, the RLP of each signed
+    transaction, b"" for a failed item; hashes (n,32) uint8 tx.Hash() or None; status (n,)): ST_BAD_RLP for
+    what does not decode, ST_INVALID_KEY for a key of 0 or >= n, ST_BODY_TOO_LARGE past 2^20 bytes.  The
+    keys' device copy is overwritten before the call returns."""
+    cid = _check_signer(chain_id, signer_kind)
+    keys = _seckey_rows(keys)
+    n = len(txs)
+    if keys.shape[0] != n:
+        raise ValueError("txs and keys batch sizes differ")
+    st = np.zeros(n, np.uint8)
+    hashes = np.zeros((n, 32), np.uint8) if want_hash else None
+    if n == 0:
+        return [], hashes, st
+    flat, off = _pack(txs)
+    G = _lib.tx_sign_growth(len(cid))
+    out = np.zeros(int(off[n]) + n * G, np.uint8)
+    olen = np.zeros(n, np.uint32)
+    cidb = np.frombuffer(cid + b"\0", np.uint8)
+    check(_lib.load().gsv_tx_sign_batch(self._h, _ptr(flat), _ptr(off), n, _ptr(keys), _ptr(cidb), len(cid),
+                                        int(signer_kind), _ptr(out), _ptr(olen), _ptr(hashes) if want_hash else None,
+                                        _ptr(st)))
+    signed = [out[int(off[i]) + i * G:int(off[i]) + i * G + int(olen[i])].tobytes() for i in range(n)]
+    return signed, hashes, st
+
+
+def tx_sign_work_bytes(n: int) -> int:
+    """bytes of the work area tx_sign_batch_dev needs (gsv.h gsv_tx_sign_work_bytes)"""
+    return int(_lib.load().gsv_tx_sign_work_bytes(n))
+
+
+def _tx_sign_batch_dev(self, rlp_t, off_t, key_t, chain_id: int, signer_kind: int, out_t, olen_t, hash_t, st_t, work_t,
+                       stream=None):
+    """torch CUDA tensors: rlp_t uint8 transactions back to back, off_t (n+1,) int64 offsets into it, key_t (n,32)
+    secret keys, out_t uint8 of off[n] + n * tx_sign_growth(chain id bytes) bytes (item i at off[i] + i * growth),
+    olen_t (n,) int32, hash_t (n,32) uint8 or None, st_t (n,) uint8, work_t uint8 of tx_sign_work_bytes(n) bytes.
+    Only enqueues on `stream`: three launches, no allocation.  key_t is the caller's to wipe."""
+    cid = _check_signer(chain_id, signer_kind)
+    n = key_t.shape[0]
+    if off_t.numel() != n + 1 or work_t.numel() < tx_sign_work_bytes(n):
+        raise ValueError("off_t holds n + 1 offsets; work_t holds tx_sign_work_bytes(n) bytes")
+    cidb = np.frombuffer(cid + b"\0", np.uint8)
+    sp = _sp(stream)
+    check(_lib.load().gsv_tx_sign_batch_dev(self._h, _tptr(rlp_t), _tptr(off_t), n, _tptr(key_t), _ptr(cidb), len(cid),
+                                            int(signer_kind), _tptr(out_t), _tptr(olen_t), _tptr(hash_t), _tptr(st_t),
+                                            _tptr(work_t), sp))
+
+
 def _point_rows(points):
     points = np.ascontiguousarray(points, np.uint8)
     if points.size % 64:
@@ -947,6 +1005,8 @@ Context.ecdsa_sign_batch = _ecdsa_sign_batch
 Context.ecdsa_sign_batch_dev = _ecdsa_sign_batch_dev
 Context.pubkey_create_batch = _pubkey_create_batch
 Context.pubkey_create_batch_dev = _pubkey_create_batch_dev
+Context.tx_sign_batch = _tx_sign_batch
+Context.tx_sign_batch_dev = _tx_sign_batch_dev
 Context.secp256k1_scalar_mul_batch = _secp256k1_scalar_mul_batch
 Context.secp256k1_scalar_mul_batch_dev = _secp256k1_scalar_mul_batch_dev
 Context.ecdh_batch = _ecdh_batch

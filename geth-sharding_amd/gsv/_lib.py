@@ -71,6 +71,13 @@ K_DERIVE_LEAF = 9
 K_HEADER = 10
 K_BN_G1 = 11
 K_ECIES = 12
+K_TX_SIGHASH = 13
+K_TX_SEAL = 14
+
+
+def tx_sign_growth(chain_id_len: int) -> int:
+    """GSV_TX_SIGN_GROWTH: the signed encoding of a transaction is at most this much longer than its input"""
+    return int(chain_id_len) + 67
 
 ECIES_OVERHEAD = 113  # GSV_ECIES_OVERHEAD: 65 (R) + 16 (IV) + 32 (tag)
 
@@ -126,6 +133,10 @@ SIGNATURES = [
     ("gsv_ecies_encrypt_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("gsv_sender_batch", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_int, _vp, _vp]),
     ("gsv_tx_sender_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, ctypes.c_int, _vp, _vp]),
+    ("gsv_tx_sign_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    ("gsv_tx_sign_work_bytes", _sz, [_sz]),
+    ("gsv_tx_sign_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _sz, ctypes.c_int, _vp, _vp, _vp, _vp,
+                                             _vp, _vp]),
     ("gsv_chunk_root_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp]),
     ("gsv_chunk_root_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
     ("gsv_bn256_pairing_check_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp]),

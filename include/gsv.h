@@ -32,6 +32,9 @@
  *                                 + crypto.ValidateSignatureValues (crypto/crypto.go:181-192)
  *   gsv_tx_sender_batch        <- types.Sender(signer, tx) (core/types/transaction_signing.go:72-89,
  *                                 127-137, 182-184, 218-220) over RLP-encoded txs
+ *   gsv_tx_sign_batch          <- types.SignTx(tx, signer, prv) (core/types/transaction_signing.go:56-63):
+ *                                 signer.Hash, crypto.Sign, tx.WithSignature (SignatureValues :141-151,
+ *                                 195-203) and tx.Hash() over RLP-encoded txs; behind keystore.SignTx
  *   gsv_keccak256_batch        <- crypto.Keccak256 (crypto/crypto.go:43-49; crypto/sha3/hashes.go:16)
  *   gsv_chunk_root_batch       <- Collation.CalculateChunkRoot (sharding/collation.go:115-119)
  *                                 = types.DeriveSha(Chunks(body)) (core/types/derive_sha.go:32-41)
@@ -119,7 +122,7 @@ extern "C" {
 #define GSV_ST_BODY_TOO_LARGE 13   /* SerializeTxToBlob's size error   sharding/collation.go:169-171 */
 #define GSV_ST_INVALID_MESSAGE 14  /* ecies.ErrInvalidMessage          ecies/ecies.go:143 */
 
-/* signer kinds for gsv_tx_sender_batch (core/types/transaction_signing.go) */
+/* signer kinds for gsv_tx_sender_batch and gsv_tx_sign_batch (core/types/transaction_signing.go) */
 #define GSV_SIGNER_EIP155 0
 #define GSV_SIGNER_HOMESTEAD 1
 #define GSV_SIGNER_FRONTIER 2
@@ -161,6 +164,11 @@ int gsv_ctx_set_timing(gsv_ctx *ctx, int enable);
  * GSV_K_END. */
 #define GSV_K_ECIES 12     /* the message half of ECIES: tag + AES-128-CTR, one launch per call */
 #define GSV_K_END 13
+/* Ids added behind GSV_K_END (its value, too, is pinned as part of ABI 2); gsv_ctx_kernel_time takes every
+ * id below GSV_K_LIMIT. */
+#define GSV_K_TX_SIGHASH 13 /* types.SignTx: decode + sighash of gsv_tx_sign_batch, one launch per call */
+#define GSV_K_TX_SEAL 14    /* types.SignTx: V, R, S, the signed encoding and tx.Hash(), one launch per call */
+#define GSV_K_LIMIT 15
 /* total milliseconds and launch count accumulated for kernel `kid` since the last reset */
 int gsv_ctx_kernel_time(gsv_ctx *ctx, int kid, double *total_ms, long *launches);
 int gsv_ctx_reset_timing(gsv_ctx *ctx);
@@ -425,6 +433,70 @@ int gsv_sender_batch(gsv_ctx *ctx, const uint8_t *sighash32, const uint8_t *r32,
 int gsv_tx_sender_batch(gsv_ctx *ctx, const uint8_t *rlp, const uint64_t *off, size_t n,
                         const uint8_t *chain_id, size_t chain_id_len, int signer_kind,
                         uint8_t *addr20_out, uint8_t *status);
+
+/* ---- types.SignTx over RLP-encoded transactions ----
+ * types.SignTx(tx, signer, prv) (core/types/transaction_signing.go:56-63): h = signer.Hash(tx), sig =
+ * crypto.Sign(h, prv), tx.WithSignature(signer, sig), for a batch.  The inverse of gsv_tx_sender_batch.
+ * Input.  tx i = rlp[off[i] .. off[i+1]) = rlp.EncodeToBytes(tx), signed or not: the nine-item list
+ *   [nonce, price, gas, to, value, data, V, R, S] (core/types/transaction.go:55-70); an unsigned
+ *   NewTransaction carries V = R = S = 0 as three 0x80 bytes.  seckey32 = n x 32 B big-endian secret keys.
+ *   One signer kind and one chain id (big-endian, length 0 = 0, at most 64 bytes, leading zero bytes
+ *   ignored) for the whole call.
+ * Decode.  The rules of gsv_tx_sender_batch (rlp/decode.go for txdata); what rlp.DecodeBytes refuses gets
+ *   GSV_ST_BAD_RLP.  The incoming V, R and S only have to decode (decodeBigInt, rlp/decode.go:271-287: any
+ *   length, no leading zero byte); their values are ignored: SignTx on a signed transaction signs it again
+ *   (transaction_signing_test.go:124), so what gsv_tx_sender_batch rejects as INVALID_SIG,
+ *   INVALID_CHAIN_ID or RECOVER_FAILED signs normally here.
+ * Hash.  EIP155Signer.Hash (:155-165): Keccak-256 of rlp([six fields, chainId, 0, 0]); FrontierSigner.Hash
+ *   (:207-216, HomesteadSigner's too): of rlp([six fields]).  A nil recipient that came as 0xc0 is hashed, and
+ *   written out, as 0x80 (rlp.Encode of the decoded struct, rlp/encode.go:552-559).
+ * Signature.  gsv_ecdsa_sign_batch's, byte for byte (RFC 6979 nonce, low s, recovery id); a key of 0 or
+ *   >= n gets GSV_ST_INVALID_KEY.
+ * Signature values (:141-151, :195-203).  R and S the 32-byte halves as big integers (leading zero bytes
+ *   dropped).  Frontier, Homestead, and EIP-155 with chain id 0: V = recid + 27 (the EIP-155 hash still
+ *   carries chainId = 0 as 0x80).  EIP-155 with another chain id: V = recid + 35 + 2 chainId, up to 65 bytes.
+ * Output.  rlp.Encode of the signed transaction in slot i, which starts at out + off[i] + i * G with
+ *   G = GSV_TX_SIGN_GROWTH(chain_id_len) and is as long as the input plus G, so `out` holds off[n] + n * G
+ *   bytes and neither a scan nor a layout call is needed.  out_len[i] = the encoding's length; txhash32_out
+ *   (may be NULL) = tx.Hash() = Keccak-256 of those bytes (transaction.go:198-206).
+ * Status precedence: GSV_ST_BAD_RLP before GSV_ST_INVALID_KEY (the reference decodes before it signs).
+ * The one deviation: an item longer than 2^20 bytes gets GSV_ST_BODY_TOO_LARGE, whatever it holds, and is
+ *   not signed; it could never enter a collation (sharding/collation.go:45, 169-171).
+ * A failed item has out_len 0 and a zero hash, and no byte of its slot is written.  No byte outside
+ *   [slot, slot + out_len[i]) is written for any item.
+ *
+ * GSV_TX_SIGN_GROWTH(chain_id_len): the signed encoding of item i is never longer than len_i + G.  The
+ * decode rules leave the six fields one encoding, so they keep their length (0xc0 -> 0x80 is one byte for
+ * one); the input's V, R, S are at least 1 byte each; the output's V is at most chain_id_len + 1 bytes
+ * of integer behind at most 2 of header, R and S at most 1 + 32 each: the payload grows by at most
+ * (chain_id_len + 3 - 1) + 2 * (33 - 1) = chain_id_len + 66 <= 130 bytes.  The input's list header is the
+ * canonical one for its payload (the decoder refuses another); a payload below 56 bytes grows to below
+ * 256 and one below 2^16 to below 2^24, so the header grows by at most 1 byte: G = chain_id_len + 67.
+ *
+ * Secret keys: as gsv_ecdsa_sign_batch states above.  The host form stages the keys FIRST in the
+ * context's device arena and overwrites that copy on the context stream before its final
+ * synchronisation, on every return that follows the copy-in; the _dev form reads the caller's buffer and
+ * writes no key material anywhere (d_work holds hashes, signatures and offsets).  The same caveat on
+ * side channels holds: this path is NOT hardened against a co-tenant observing timing or memory traffic.
+ *
+ * Argument errors, before any HIP call: GSV_E_INVALID_ARG for a NULL context, chain_id_len > 64, a NULL
+ * chain id with a length, a signer kind that is none of GSV_SIGNER_*. */
+#define GSV_TX_SIGN_GROWTH(chain_id_len) ((size_t)(chain_id_len) + 67)
+int gsv_tx_sign_batch(gsv_ctx *ctx, const uint8_t *rlp, const uint64_t *off, size_t n, const uint8_t *seckey32,
+                      const uint8_t *chain_id, size_t chain_id_len, int signer_kind, uint8_t *out,
+                      uint32_t *out_len, uint8_t *txhash32_out, uint8_t *status);
+/* Device-resident form: every array in HBM, d_off = n + 1 ascending uint64 offsets into d_rlp as in
+ * gsv_keccak256_batch_dev (slot i at d_out + d_off[i] + i * G), d_out_len n x uint32, d_txhash32_out may
+ * be NULL (else 4-byte aligned), d_work = gsv_tx_sign_work_bytes(n) bytes of the caller's, 16-byte
+ * aligned.  It only enqueues on `stream` (NULL = the context stream): three launches, k_tx_sighash
+ * (GSV_K_TX_SIGHASH), the signature kernel of gsv_ecdsa_sign_batch_dev (GSV_K_ECRECOVER), k_tx_seal
+ * (GSV_K_TX_SEAL), handing each other hashes, signatures and a 16-byte record per item through d_work.
+ * No allocation, no synchronisation, no prepare call: the chain id travels as kernel arguments. */
+size_t gsv_tx_sign_work_bytes(size_t n);
+int gsv_tx_sign_batch_dev(gsv_ctx *ctx, const uint8_t *d_rlp, const uint64_t *d_off, size_t n,
+                          const uint8_t *d_seckey32, const uint8_t *chain_id, size_t chain_id_len,
+                          int signer_kind, uint8_t *d_out, uint32_t *d_out_len, uint8_t *d_txhash32_out,
+                          uint8_t *d_status, uint8_t *d_work, void *stream);
 
 /* ---- collation chunk root (B1-B5) ----
  * body i = bodies[off[i] .. off[i+1]), each <= 2^20 bytes (else GSV_E_TOO_LARGE).
