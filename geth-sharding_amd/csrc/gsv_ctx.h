@@ -3,6 +3,7 @@
 //   gsv_batch.hip    stateless batches: Keccak, ecrecover and its precompile, bn256 add / mul, senders
 //   gsv_ecies.hip    ecies.Encrypt / Decrypt: the launch chains around the ladder
 //   gsv_txsign.hip   types.SignTx: the launch chain around the signature kernel
+//   gsv_modexp.hip   the modexp precompile: host grouping by modulus width, one launch per class
 //   gsv_trie.hip     chunk root, DeriveSha, Proof of Custody, collation headers
 //   gsv_pairing.hip  BN254 pairing check
 //   gsv_notary.hip   notary validation, shard partition + RCCL all-gather
@@ -188,8 +189,8 @@ struct gsv_ctx {
     struct Pending { int kid; hipEvent_t a, b; };
     std::vector<Pending> pending;
     std::vector<hipEvent_t> free_events;
-    double total_ms[GSV_K_LIMIT] = {0};
-    long launches[GSV_K_LIMIT] = {0};
+    double total_ms[GSV_K_BOUND] = {0};
+    long launches[GSV_K_BOUND] = {0};
     std::mutex tmu;
     std::vector<hipEvent_t> open_ev;  // timer events opened by launch hooks
     hipStream_t cur_stream = nullptr;  // stream of the shape run in progress (launch hooks)

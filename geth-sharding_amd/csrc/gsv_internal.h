@@ -141,6 +141,11 @@ hipError_t launch_bn256_g1_add(const uint8_t* d_in128, uint32_t n, uint8_t* d_ou
 hipError_t launch_bn256_g1_mul(const uint8_t* d_in96, uint32_t n, uint8_t* d_out64, uint8_t* d_status,
                                int bitserial, hipStream_t st);
 
+// modexp.hip: the bigModExp precompile over n rows of base || exp || mod (bl + el + ml bytes, each length
+// <= 1024), n rows of ml bytes out; d_work = mdx::work_bytes(n, ml) bytes (modexp_plan.h), 4-byte aligned
+hipError_t launch_modexp(const uint8_t* d_in, uint32_t n, uint32_t bl, uint32_t el, uint32_t ml, uint8_t* d_out,
+                         uint8_t* d_work, hipStream_t st);
+
 // collation.hip: CollationHeader.Hash() with ProposerSignature empty (k_header_hash alone: the hash the
 // proposer signs), no nil fields
 hipError_t launch_header_hash_unsigned(const uint8_t* d_sid32, const uint8_t* d_root32, const uint8_t* d_per32,

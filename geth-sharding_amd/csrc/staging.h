@@ -143,6 +143,13 @@ struct RecordStage {
     B8 in, out, st;
     RecordStage(Layout& L, size_t n, size_t rec, size_t res) : in(L.buf(n * rec)), out(L.buf(n * res)), st(L.buf(n)) {}
 };
+// gsv_modexp_batch, once per width class: the rows base || exp || mod of the class's items, their
+// results, and the device form's work buffer (gsv_modexp_work_bytes; none for the 32-byte class)
+struct ModexpStage {
+    B8 in, out, work;
+    ModexpStage(Layout& L, size_t in_bytes, size_t out_bytes, size_t work_bytes)
+        : in(L.buf(in_bytes)), out(L.buf(out_bytes)), work(L.buf(work_bytes, work_bytes != 0)) {}
+};
 struct SenderStage {  // gsv_sender_batch, and the tail of tx_sender_impl
     B8 h, r, s;
     Buf<uint64_t> v;

@@ -981,6 +981,61 @@ def _ecies_encrypt_batch_dev(self, msg_t, msg_off_t, pub_t, eph_t, iv_t, s2_t, s
                                                   _tptr(work_t), sp))
 
 
+def modexp_output_layout(inputs):
+    """(out_off uint64[n+1], status uint8[n]) of a batch of modexp precompile inputs (gsv.h
+    gsv_modexp_output_layout; host only): item i's output is out_off[i+1] - out_off[i] = modLen_i bytes, 0
+    with ST_MODEXP_TOO_LONG when one of its lengths is above MODEXP_MAX_LEN."""
+    n = len(inputs)
+    flat, off = _pack(inputs)
+    out_off = np.zeros(n + 1, np.uint64)
+    st = np.zeros(n, np.uint8)
+    check(_lib.load().gsv_modexp_output_layout(_ptr(flat), _ptr(off), n, _ptr(out_off), _ptr(st)))
+    return out_off, st
+
+
+def _modexp_batch(self, inputs):
+    """The bigModExp precompile (0x05) over a batch (gsv.h gsv_modexp_batch): inputs as the precompile
+    receives them.  Returns (outputs: list of bytes, modLen_i bytes each; status (n,) uint8: ST_OK, or
+    ST_MODEXP_TOO_LONG with an empty output for an item with a length above MODEXP_MAX_LEN)."""
+    inputs = [bytes(x) for x in inputs]
+    n = len(inputs)
+    if n == 0:
+        return [], np.zeros(0, np.uint8)
+    flat, off = _pack(inputs)
+    out_off = np.zeros(n + 1, np.uint64)
+    st = np.zeros(n, np.uint8)
+    L = _lib.load()
+    check(L.gsv_modexp_output_layout(_ptr(flat), _ptr(off), n, _ptr(out_off), _ptr(st)))
+    out = np.zeros(int(out_off[n]) + 8, np.uint8)
+    check(L.gsv_modexp_batch(self._h, _ptr(flat), _ptr(off), n, _ptr(out), _ptr(out_off), _ptr(st)))
+    return [out[int(out_off[i]):int(out_off[i + 1])].tobytes() for i in range(n)], st
+
+
+def modexp_work_bytes(n: int, base_len: int, exp_len: int, mod_len: int) -> int:
+    """bytes of the work buffer modexp_batch_dev needs for this shape (gsv.h gsv_modexp_work_bytes)"""
+    return int(_lib.load().gsv_modexp_work_bytes(int(n), int(base_len), int(exp_len), int(mod_len)))
+
+
+def _modexp_batch_dev(self, in_t, base_len: int, exp_len: int, mod_len: int, out_t, work_t=None, stream=None):
+    """torch CUDA uint8 tensors: in_t (n, base_len + exp_len + mod_len) rows of base || exp || mod (any byte
+    alignment), out_t (n, mod_len), work_t of modexp_work_bytes(...) bytes, 4-byte aligned (None where that is
+    0).  Only enqueues on `stream`: one launch, no allocation."""
+    for v in (base_len, exp_len, mod_len):
+        if not 0 <= int(v) <= _lib.MODEXP_MAX_LEN:
+            raise ValueError("modexp: each length is at most MODEXP_MAX_LEN bytes")
+    row = int(base_len) + int(exp_len) + int(mod_len)
+    n = int(in_t.shape[0])
+    if not in_t.is_contiguous() or not out_t.is_contiguous() or in_t.numel() != n * row or \
+            out_t.numel() != n * int(mod_len):
+        raise ValueError("in_t is n contiguous rows of base_len + exp_len + mod_len bytes, out_t n rows of mod_len")
+    need = modexp_work_bytes(n, base_len, exp_len, mod_len)
+    if need and (work_t is None or work_t.numel() * work_t.element_size() < need):
+        raise ValueError("work_t holds modexp_work_bytes(n, base_len, exp_len, mod_len) bytes")
+    sp = _sp(stream)
+    check(_lib.load().gsv_modexp_batch_dev(self._h, _tptr(in_t), n, int(base_len), int(exp_len), int(mod_len),
+                                           _tptr(out_t), _tptr(work_t), sp))
+
+
 def _arena_read(self, off, n):
     """Test hook (gsv.h gsv_ctx_arena_read): n bytes of the staging arena from `off`, as they are now."""
     out = np.zeros(n, np.uint8)
@@ -1015,6 +1070,8 @@ Context.ecies_decrypt_batch = _ecies_decrypt_batch
 Context.ecies_encrypt_batch = _ecies_encrypt_batch
 Context.ecies_decrypt_batch_dev = _ecies_decrypt_batch_dev
 Context.ecies_encrypt_batch_dev = _ecies_encrypt_batch_dev
+Context.modexp_batch = _modexp_batch
+Context.modexp_batch_dev = _modexp_batch_dev
 Context._arena_read = _arena_read
 Context.prepared_shapes = _prepared_shapes
 Context.bn256_add_batch = _bn256_add_batch

@@ -29,6 +29,7 @@ ST_INVALID_KEY = 11
 ST_INVALID_CURVE = 12
 ST_BODY_TOO_LARGE = 13
 ST_INVALID_MESSAGE = 14
+ST_MODEXP_TOO_LONG = 15
 
 # a short text per per-item status: the reference's error string where it has one (include/gsv.h names
 # the sources)
@@ -48,6 +49,7 @@ STATUS_STRINGS = {
     ST_INVALID_CURVE: "ecies: invalid elliptic curve",
     ST_BODY_TOO_LARGE: "serialized body size exceeds the collation size limit",
     ST_INVALID_MESSAGE: "ecies: invalid message",
+    ST_MODEXP_TOO_LONG: "modexp: a length above GSV_MODEXP_MAX_LEN",
 }
 
 SIGNER_EIP155 = 0
@@ -73,6 +75,9 @@ K_BN_G1 = 11
 K_ECIES = 12
 K_TX_SIGHASH = 13
 K_TX_SEAL = 14
+K_MODEXP = 15
+
+MODEXP_MAX_LEN = 1024  # GSV_MODEXP_MAX_LEN: the cap on baseLen, expLen and modLen of the modexp precompile
 
 
 def tx_sign_growth(chain_id_len: int) -> int:
@@ -168,6 +173,11 @@ SIGNATURES = [
     ("gsv_bn256_add_batch_dev", ctypes.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
     ("gsv_bn256_scalar_mul_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
     ("gsv_bn256_scalar_mul_batch_dev", ctypes.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    ("gsv_modexp_output_layout", ctypes.c_int, [_vp, _vp, _sz, _vp, _vp]),
+    ("gsv_modexp_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    ("gsv_modexp_work_bytes", _sz, [_sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
+    ("gsv_modexp_batch_dev", ctypes.c_int, [_vp, _vp, _sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp,
+                                            _vp]),
     ("gsv_chunk_root_prepare", ctypes.c_int, [_vp, _vp, _sz]),
     ("gsv_bn256_pairing_prepare", ctypes.c_int, [_vp, _vp, _sz]),
     ("gsv_notary_prepare", ctypes.c_int, [_vp, _vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_uint32]),

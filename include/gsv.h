@@ -60,6 +60,8 @@
  *                                 = G1.Unmarshal x 2, G1.Add, G1.Marshal (crypto/bn256/cloudflare/bn256.go:62-67)
  *   gsv_bn256_scalar_mul_batch <- the bn256ScalarMul precompile's Run (core/vm/contracts.go:297-312)
  *                                 = G1.Unmarshal, G1.ScalarMult, G1.Marshal (bn256.go:70-78)
+ *   gsv_modexp_batch           <- the bigModExp precompile's Run (core/vm/contracts.go:226-252, EIP-198)
+ *                                 = big.Int.Exp(base, exp, mod) over operands of caller-chosen length
  *
  * Conventions
  *   - Return value: GSV_SUCCESS (0) or a negative GSV_E_* API/HIP error. A bad ITEM never fails
@@ -121,6 +123,7 @@ extern "C" {
 #define GSV_ST_INVALID_CURVE 12    /* ecies.ErrInvalidCurve            ecies/ecies.go:47 */
 #define GSV_ST_BODY_TOO_LARGE 13   /* SerializeTxToBlob's size error   sharding/collation.go:169-171 */
 #define GSV_ST_INVALID_MESSAGE 14  /* ecies.ErrInvalidMessage          ecies/ecies.go:143 */
+#define GSV_ST_MODEXP_TOO_LONG 15  /* a modexp length above GSV_MODEXP_MAX_LEN: not the reference's, see there */
 
 /* signer kinds for gsv_tx_sender_batch and gsv_tx_sign_batch (core/types/transaction_signing.go) */
 #define GSV_SIGNER_EIP155 0
@@ -169,6 +172,10 @@ int gsv_ctx_set_timing(gsv_ctx *ctx, int enable);
 #define GSV_K_TX_SIGHASH 13 /* types.SignTx: decode + sighash of gsv_tx_sign_batch, one launch per call */
 #define GSV_K_TX_SEAL 14    /* types.SignTx: V, R, S, the signed encoding and tx.Hash(), one launch per call */
 #define GSV_K_LIMIT 15
+/* Ids added behind GSV_K_LIMIT (pinned like the two before it); gsv_ctx_kernel_time takes every id below
+ * GSV_K_BOUND. */
+#define GSV_K_MODEXP 15     /* the modexp precompile: one launch per call of the device form */
+#define GSV_K_BOUND 16
 /* total milliseconds and launch count accumulated for kernel `kid` since the last reset */
 int gsv_ctx_kernel_time(gsv_ctx *ctx, int kid, double *total_ms, long *launches);
 int gsv_ctx_reset_timing(gsv_ctx *ctx);
@@ -541,6 +548,46 @@ int gsv_bn256_add_batch_dev(gsv_ctx *ctx, const uint8_t *d_in128, size_t n, uint
                             void *stream);
 int gsv_bn256_scalar_mul_batch_dev(gsv_ctx *ctx, const uint8_t *d_in96, size_t n, uint8_t *d_out64,
                                    uint8_t *d_status, void *stream);
+
+/* ---- modular exponentiation: the bigModExp (0x05) precompile (core/vm/contracts.go:226-252, EIP-198) ----
+ * Input i = in[off[i] .. off[i+1]) exactly as the precompile receives it, every read right-padded with
+ * zeros (getData, core/vm/common.go:37-47):
+ *   - baseLen, expLen, modLen are the LOW 64 BITS of the 32-byte big-endian words at 0, 32 and 64
+ *     (new(big.Int).SetBytes(...).Uint64(), :228-230): bytes 0..23 of a length word are ignored, and an
+ *     input shorter than 96 bytes has its missing header bytes read as zeros (the empty input: 0, 0, 0).
+ *   - body = input[96:] (:232-236); base, exp, mod are the big-endian values of getData(body, 0, baseLen),
+ *     getData(body, baseLen, expLen), getData(body, baseLen + expLen, modLen) (:243-245).  A body shorter
+ *     than declared is right-padded, which CHANGES THE VALUES (a cut modulus gets zero low bytes).
+ *   - baseLen == 0 && modLen == 0: the empty output (:238-240).  mod == 0: modLen zero bytes (:247-250).
+ *     Else LeftPadBytes(base.Exp(base, exp, mod).Bytes(), modLen) (:251): always exactly modLen bytes.
+ *     x^0 mod m = 1 mod m (0 for m == 1), 0^0 included; the base may be longer and larger than the
+ *     modulus; any modulus > 0 is legal, odd, even or a power of two.
+ * The one departure: the reference would try to allocate whatever length it is told.  Here each of the
+ * three lengths is capped at GSV_MODEXP_MAX_LEN bytes (the largest modulus of the reference's own vectors,
+ * core/vm/contracts_test.go:36-116, and the top case of its gas formula).  An item with ANY length above the
+ * cap gets status GSV_ST_MODEXP_TOO_LONG and an empty output; the batch still succeeds and the caller runs
+ * that item elsewhere.  Every other item has status GSV_ST_OK.  The exponent is public: the time taken
+ * depends on it.  No prepare call. */
+#define GSV_MODEXP_MAX_LEN 1024
+/* Host only, no context: out_off[0..n] (out_off[0] = 0; item i's output is modLen_i bytes, 0 if over the
+ * cap), status[i] = GSV_ST_OK or GSV_ST_MODEXP_TOO_LONG. */
+int gsv_modexp_output_layout(const uint8_t *in, const uint64_t *off, size_t n, uint64_t *out_off, uint8_t *status);
+/* out is packed by out_off, which must be what gsv_modexp_output_layout gives for the same input (else
+ * GSV_E_INVALID_ARG); status as there.  Items are grouped by the width class of modLen (32, 64, 128, 256,
+ * 512, 1024 bytes) and each non-empty class is one call of the device form over rows left-padded with
+ * zero bytes to the class's longest base, exponent and modulus.  Items with modLen == 0 and items over
+ * the cap touch no device memory. */
+int gsv_modexp_batch(gsv_ctx *ctx, const uint8_t *in, const uint64_t *off, size_t n, uint8_t *out,
+                     const uint64_t *out_off, uint8_t *status);
+/* Device-resident, one shape per call: d_in = n rows of base_len + exp_len + mod_len bytes (base || exp ||
+ * mod, no 96-byte header, any byte alignment), d_out = n rows of mod_len bytes, d_work =
+ * gsv_modexp_work_bytes(...) bytes of the caller's, 4-byte aligned (may be NULL when that is 0).  Only
+ * enqueues, one launch (GSV_K_MODEXP), no allocation, capturable, no prepare call.  n == 0 or mod_len == 0:
+ * success, nothing enqueued.  A length above the cap, or a NULL buffer where there is work:
+ * GSV_E_INVALID_ARG.  No status output: every row is a legal item (mod == 0 gives zeros). */
+size_t gsv_modexp_work_bytes(size_t n, uint32_t base_len, uint32_t exp_len, uint32_t mod_len);
+int gsv_modexp_batch_dev(gsv_ctx *ctx, const uint8_t *d_in, size_t n, uint32_t base_len, uint32_t exp_len,
+                         uint32_t mod_len, uint8_t *d_out, uint8_t *d_work, void *stream);
 
 /* ---- synthetic signed workload (bench / test data generator; signing is not on the path) ----
  * key_i, msg_i, nonce_i = Keccak256(le64(seed) || le64(i) || "key"/"msg"/"nce"), key and nonce
