@@ -189,8 +189,8 @@ struct gsv_ctx {
     struct Pending { int kid; hipEvent_t a, b; };
     std::vector<Pending> pending;
     std::vector<hipEvent_t> free_events;
-    double total_ms[GSV_K_BOUND] = {0};
-    long launches[GSV_K_BOUND] = {0};
+    double total_ms[GSV_K_CAP] = {0};
+    long launches[GSV_K_CAP] = {0};
     std::mutex tmu;
     std::vector<hipEvent_t> open_ev;  // timer events opened by launch hooks
     hipStream_t cur_stream = nullptr;  // stream of the shape run in progress (launch hooks)

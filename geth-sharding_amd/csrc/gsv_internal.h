@@ -80,6 +80,10 @@ hipError_t launch_ecies_seal(const uint8_t* msg, const uint64_t* msg_off, const 
 hipError_t launch_keccak256(const uint8_t* data, const uint64_t* off, uint32_t n, uint8_t* out32,
                             hipStream_t st);
 
+// hash_md.hip: SHA-256 rows, and RIPEMD-160 rows of 12 zero bytes and the 20-byte digest
+hipError_t launch_sha256(const uint8_t* data, const uint64_t* off, uint32_t n, uint8_t* out32, hipStream_t st);
+hipError_t launch_ripemd160(const uint8_t* data, const uint64_t* off, uint32_t n, uint8_t* out32, hipStream_t st);
+
 // Launchers call timer_begin(tctx, GSV_HOOK_TAIL) (no launch follows it directly) where the call's
 // bulk kernels end and its latency-bound tail begins (trie top, Miller loop + final exponentiation):
 // with pipelined shape instances the next call's bulk kernels start there (gsv_ctx.h shape_run).

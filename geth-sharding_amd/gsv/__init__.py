@@ -139,6 +139,25 @@ class Context:
         check(_lib.load().gsv_keccak256_batch(self._h, _ptr(flat), _ptr(off), n, _ptr(out)))
         return out
 
+    # -------------------------------------------------------------- SHA-256, RIPEMD-160
+    def _md_batch(self, fn, msgs) -> np.ndarray:
+        n = len(msgs)
+        out = np.zeros((n, 32), np.uint8)
+        if n == 0:
+            return out
+        flat, off = _pack(msgs)
+        check(fn(self._h, _ptr(flat), _ptr(off), n, _ptr(out)))
+        return out
+
+    def sha256_batch(self, msgs) -> np.ndarray:
+        """(n, 32) uint8: SHA-256 of each message (gsv.h gsv_sha256_batch)"""
+        return self._md_batch(_lib.load().gsv_sha256_batch, msgs)
+
+    def ripemd160_batch(self, msgs) -> np.ndarray:
+        """(n, 32) uint8: the ripemd160hash precompile's row of each message, 12 zero bytes and the 20-byte
+        RIPEMD-160 digest (gsv.h gsv_ripemd160_batch)"""
+        return self._md_batch(_lib.load().gsv_ripemd160_batch, msgs)
+
     # -------------------------------------------------------------- secp256k1
     def ecrecover_batch(self, msg32, sig65, want_pub=True, want_addr=False):
         """msg32 (n,32) uint8, sig65 (n,65) uint8 -> (pub65 (n,65) | None, addr20 (n,20) | None,
@@ -220,6 +239,19 @@ class Context:
         check(_lib.load().gsv_keccak256_batch_dev(self._h, ctypes.c_void_p(data_t.data_ptr()),
                                                   ctypes.c_void_p(off_t.data_ptr()), n,
                                                   ctypes.c_void_p(out_t.data_ptr()), sp))
+
+    def sha256_batch_dev(self, data_t, off_t, out_t, stream=None):
+        """torch CUDA tensors: data_t uint8 messages back to back, off_t (n+1,) int64 offsets into it, out_t
+        (n,32) uint8; only enqueues on `stream`."""
+        check(_lib.load().gsv_sha256_batch_dev(self._h, ctypes.c_void_p(data_t.data_ptr()),
+                                               ctypes.c_void_p(off_t.data_ptr()), out_t.shape[0],
+                                               ctypes.c_void_p(out_t.data_ptr()), _sp(stream)))
+
+    def ripemd160_batch_dev(self, data_t, off_t, out_t, stream=None):
+        """As sha256_batch_dev; row i of out_t is 12 zero bytes and the 20-byte digest."""
+        check(_lib.load().gsv_ripemd160_batch_dev(self._h, ctypes.c_void_p(data_t.data_ptr()),
+                                                  ctypes.c_void_p(off_t.data_ptr()), out_t.shape[0],
+                                                  ctypes.c_void_p(out_t.data_ptr()), _sp(stream)))
 
 
 def _be(x: int) -> bytes:

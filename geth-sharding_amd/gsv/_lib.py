@@ -76,6 +76,8 @@ K_ECIES = 12
 K_TX_SIGHASH = 13
 K_TX_SEAL = 14
 K_MODEXP = 15
+K_SHA256 = 16
+K_RIPEMD160 = 17
 
 MODEXP_MAX_LEN = 1024  # GSV_MODEXP_MAX_LEN: the cap on baseLen, expLen and modLen of the modexp precompile
 
@@ -116,6 +118,10 @@ SIGNATURES = [
     ("gsv_ctx_reset_timing", ctypes.c_int, [_vp]),
     ("gsv_keccak256_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp]),
     ("gsv_keccak256_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    ("gsv_sha256_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp]),
+    ("gsv_sha256_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    ("gsv_ripemd160_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp]),
+    ("gsv_ripemd160_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
     ("gsv_ecrecover_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     ("gsv_ecrecover_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("gsv_ecdsa_verify_batch", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp]),

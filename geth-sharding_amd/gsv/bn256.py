@@ -62,6 +62,11 @@ class Bn256Pairing:
             raise ErrMalformedPoint("bn256: malformed point")
         return TRUE32 if v == _lib.PAIRING_TRUE else FALSE32
 
+    def RunBatch(self, inputs, ctx=None) -> np.ndarray:
+        """(n,) uint8 verdicts PAIRING_FALSE / PAIRING_TRUE / PAIRING_BAD_INPUT of inputs whose lengths are
+        multiples of 192 (Run refuses the others before the device): one pairing_check_batch call"""
+        return PairingCheckBatch([bytes(x) for x in inputs], ctx)
+
 
 def G1Add(a: bytes, b: bytes, ctx=None) -> bytes:
     """Marshal(Unmarshal(a) + Unmarshal(b)) over 64-byte G1 encodings (bn256.go:62-67)."""
@@ -87,6 +92,11 @@ class Bn256Add:
             raise ErrMalformedPoint("bn256: malformed point")
         return out[0].tobytes()
 
+    def RunBatch(self, inputs, ctx=None):
+        """(out (n,64) uint8, status (n,)): ST_BN_BAD_INPUT and a zero row where Run raises; one
+        bn256_add_batch call"""
+        return (ctx or default_context()).bn256_add_batch([bytes(x) for x in inputs])
+
 
 class Bn256ScalarMul:
     """PrecompiledContract{RequiredGas, Run} for address 0x07 (core/vm/contracts.go:291-312)."""
@@ -101,3 +111,7 @@ class Bn256ScalarMul:
         if st[0] != _lib.ST_OK:  # newCurvePoint error (contracts.go:299-303)
             raise ErrMalformedPoint("bn256: malformed point")
         return out[0].tobytes()
+
+    def RunBatch(self, inputs, ctx=None):
+        """(out (n,64) uint8, status (n,)) as Bn256Add.RunBatch; one bn256_scalar_mul_batch call"""
+        return (ctx or default_context()).bn256_scalar_mul_batch([bytes(x) for x in inputs])

@@ -6,6 +6,8 @@
     SigToPub(hash, sig)         crypto/signature_cgo.go:36-44 (returns the 65-byte key here)
     EcrecoverBatch(...)         batch form used by the notary / tx pool hooks
     Keccak256Batch(msgs)        batch form
+    Sha256(data) / Sha256Batch(msgs)        crypto/sha256.Sum256, as core/vm/contracts.go:114-117 calls it
+    Ripemd160(data) / Ripemd160Batch(msgs)  ripemd160.New().Write(data).Sum(nil), as contracts.go:129-133 does
     Ecrecover precompile        core/vm/contracts.go:70-101 (EcrecoverPrecompile.Run / RunBatch)
     VerifySignature(pub, hash, sig)   crypto/signature_cgo.go:63-68 -> secp256k1.VerifySignature
     VerifySignatureBatch(...)   batch form
@@ -53,6 +55,24 @@ Keccak256Hash = Keccak256
 
 def Keccak256Batch(msgs, ctx=None) -> np.ndarray:
     return (ctx or default_context()).keccak256_batch(list(msgs))
+
+
+def Sha256Batch(msgs, ctx=None) -> np.ndarray:
+    """(n, 32) uint8: the SHA-256 digest of each message"""
+    return (ctx or default_context()).sha256_batch([bytes(m) for m in msgs])
+
+
+def Sha256(data: bytes, ctx=None) -> bytes:
+    return bytes(Sha256Batch([data], ctx)[0])
+
+
+def Ripemd160Batch(msgs, ctx=None) -> np.ndarray:
+    """(n, 20) uint8: the RIPEMD-160 digest of each message (the library's rows without their 12 zero bytes)"""
+    return (ctx or default_context()).ripemd160_batch([bytes(m) for m in msgs])[:, 12:]
+
+
+def Ripemd160(data: bytes, ctx=None) -> bytes:
+    return bytes(Ripemd160Batch([data], ctx)[0])
 
 
 def _check_lengths(msg: bytes, sig: bytes):

@@ -62,6 +62,11 @@
  *                                 = G1.Unmarshal, G1.ScalarMult, G1.Marshal (bn256.go:70-78)
  *   gsv_modexp_batch           <- the bigModExp precompile's Run (core/vm/contracts.go:226-252, EIP-198)
  *                                 = big.Int.Exp(base, exp, mod) over operands of caller-chosen length
+ *   gsv_sha256_batch           <- the sha256hash precompile's Run (core/vm/contracts.go:114-117)
+ *                                 = crypto/sha256.Sum256
+ *   gsv_ripemd160_batch        <- the ripemd160hash precompile's Run (core/vm/contracts.go:129-133)
+ *                                 = common.LeftPadBytes(ripemd160.New().Write(input).Sum(nil), 32)
+ *                                 (vendor/golang.org/x/crypto/ripemd160)
  *
  * Conventions
  *   - Return value: GSV_SUCCESS (0) or a negative GSV_E_* API/HIP error. A bad ITEM never fails
@@ -176,6 +181,11 @@ int gsv_ctx_set_timing(gsv_ctx *ctx, int enable);
  * GSV_K_BOUND. */
 #define GSV_K_MODEXP 15     /* the modexp precompile: one launch per call of the device form */
 #define GSV_K_BOUND 16
+/* Ids added behind GSV_K_BOUND (pinned like the three before it); gsv_ctx_kernel_time takes every id below
+ * GSV_K_CAP. */
+#define GSV_K_SHA256 16     /* the sha256hash precompile: one launch per call */
+#define GSV_K_RIPEMD160 17  /* the ripemd160hash precompile: one launch per call */
+#define GSV_K_CAP 18
 /* total milliseconds and launch count accumulated for kernel `kid` since the last reset */
 int gsv_ctx_kernel_time(gsv_ctx *ctx, int kid, double *total_ms, long *launches);
 int gsv_ctx_reset_timing(gsv_ctx *ctx);
@@ -220,6 +230,25 @@ int gsv_ctx_stream_count(gsv_ctx *ctx, int *user_streams, int *side_streams);
 int gsv_keccak256_batch(gsv_ctx *ctx, const uint8_t *data, const uint64_t *off, size_t n,
                         uint8_t *out32);
 int gsv_keccak256_batch_dev(gsv_ctx *ctx, const uint8_t *d_data, const uint64_t *d_off, size_t n,
+                            uint8_t *d_out32, void *stream);
+
+/* ---- SHA-256 and RIPEMD-160: the sha256hash (0x02) and ripemd160hash (0x03) precompiles ----
+ * Message i is data[off[i] .. off[i+1]), as for gsv_keccak256_batch; n == 0 is a success that launches
+ * nothing.  Neither hash can fail per item, so there is no status output.
+ *   sha256:    out32[32*i .. +32) = SHA-256(message i) (core/vm/contracts.go:114-117).
+ *   ripemd160: out32[32*i .. +32) = the precompile's row (contracts.go:129-133): 12 zero bytes, then the
+ *              20-byte RIPEMD-160 digest of message i (common.LeftPadBytes(.., 32)).  The plain digest is
+ *              bytes 12 .. 32 of the row; there is no 20-byte form.
+ * The host forms stage, run and copy back.  The _dev forms take device arrays (the n + 1 offsets
+ * included), any byte alignment of d_data and d_out32, and only enqueue one launch (GSV_K_SHA256 /
+ * GSV_K_RIPEMD160) on `stream` (NULL = the context stream): no allocation, no synchronisation, no
+ * prepare call, capturable.  They read no byte outside d_data[d_off[0] .. d_off[n]) but for the other
+ * bytes of the aligned dwords that hold its first and its last byte. */
+int gsv_sha256_batch(gsv_ctx *ctx, const uint8_t *data, const uint64_t *off, size_t n, uint8_t *out32);
+int gsv_sha256_batch_dev(gsv_ctx *ctx, const uint8_t *d_data, const uint64_t *d_off, size_t n,
+                         uint8_t *d_out32, void *stream);
+int gsv_ripemd160_batch(gsv_ctx *ctx, const uint8_t *data, const uint64_t *off, size_t n, uint8_t *out32);
+int gsv_ripemd160_batch_dev(gsv_ctx *ctx, const uint8_t *d_data, const uint64_t *d_off, size_t n,
                             uint8_t *d_out32, void *stream);
 
 /* ---- secp256k1 public-key recovery (A5-A9) ----
