@@ -4,6 +4,7 @@
 //   gsv_ecies.hip    ecies.Encrypt / Decrypt: the launch chains around the ladder
 //   gsv_txsign.hip   types.SignTx: the launch chain around the signature kernel
 //   gsv_modexp.hip   the modexp precompile: host grouping by modulus width, one launch per class
+//   gsv_ethash.hip   ethash: dataset items, hashimotoLight, VerifySeal; the host forms' epoch caches
 //   gsv_trie.hip     chunk root, DeriveSha, Proof of Custody, collation headers
 //   gsv_pairing.hip  BN254 pairing check
 //   gsv_notary.hip   notary validation, shard partition + RCCL all-gather
@@ -189,8 +190,8 @@ struct gsv_ctx {
     struct Pending { int kid; hipEvent_t a, b; };
     std::vector<Pending> pending;
     std::vector<hipEvent_t> free_events;
-    double total_ms[GSV_K_CAP] = {0};
-    long launches[GSV_K_CAP] = {0};
+    double total_ms[GSV_K_TOP] = {0};
+    long launches[GSV_K_TOP] = {0};
     std::mutex tmu;
     std::vector<hipEvent_t> open_ev;  // timer events opened by launch hooks
     hipStream_t cur_stream = nullptr;  // stream of the shape run in progress (launch hooks)
@@ -220,6 +221,15 @@ struct gsv_ctx {
     std::vector<hipStream_t> user_streams;
     std::mutex qmu;
     int pipeline_depth = 1;  // instances per prepared shape (gsv_ctx_set_pipeline_depth)
+    // the ethash host forms' verification caches on the device, most recently used first, at most
+    // GSV_ETHASH_MAX_CACHES (gsv_ethash.hip); guarded by mu
+    struct EthashCache {
+        uint64_t epoch;
+        bool test;
+        uint8_t* d;
+        uint64_t bytes;
+    };
+    std::list<EthashCache> ethash_caches;
 };
 
 namespace gsv {

@@ -1,0 +1,219 @@
+// ethash of the C ABI (gsv_ctx.h): the device forms check their arguments and enqueue one launch of
+// ethash.hip; the host forms group a batch by epoch, keep the epochs' verification caches on the device
+// (made on the host by ethash_host.h, outside the context's lock) and run one launch per epoch.
+#include <map>
+
+#include "ethash_host.h"
+#include "gsv_ctx.h"
+
+using namespace gsv::api;
+namespace eth = gsv::ethash;
+
+namespace {
+
+constexpr uint64_t MAX_DATASET = 1ull << 38;  // rows <= 2^31: 2 parent + 1 fits 32 bits
+constexpr uint64_t MAX_N = 0x7FFFFFFFull;     // two lanes per header in a 32-bit grid
+
+bool cache_ok(const uint8_t* d_cache, uint64_t cache_bytes) {
+    return d_cache && ((uintptr_t)d_cache & 15) == 0 && cache_bytes >= eth::HASH_BYTES &&
+           cache_bytes % eth::HASH_BYTES == 0 && cache_bytes < MAX_DATASET;
+}
+
+bool dataset_ok(uint64_t dataset_bytes) {
+    return dataset_bytes >= eth::MIX_BYTES && dataset_bytes % eth::MIX_BYTES == 0 && dataset_bytes <= MAX_DATASET;
+}
+
+bool seed_ok(const uint8_t* d_hash32, const uint64_t* d_nonce) {
+    return d_hash32 && d_nonce && ((uintptr_t)d_hash32 & 3) == 0 && ((uintptr_t)d_nonce & 7) == 0;
+}
+
+// the first full-size epoch whose dataset no longer fits MAX_DATASET: the host forms refuse it (and every
+// later one) before sizing anything
+constexpr uint64_t MAX_EPOCH = (MAX_DATASET - eth::DATASET_INIT_BYTES) / eth::DATASET_GROWTH_BYTES;
+
+struct EpochSizes {
+    uint64_t cache_bytes, dataset_bytes;
+};
+
+EpochSizes epoch_sizes(uint64_t epoch, bool test) {
+    if (test) return {eth::TEST_CACHE_BYTES, eth::TEST_DATASET_BYTES};
+    return {eth::calc_cache_size(epoch), eth::calc_dataset_size(epoch)};
+}
+
+// The device cache of (epoch, test), called with the context's lock held.  On a miss the lock is dropped
+// while the host generates the cache (a second for a full-size epoch: ADVICE's second finding, no long
+// work under the mutex), then the list is searched again.  Every host form synchronises before it
+// releases the lock, so whoever holds it knows that no launch is reading any cached pointer: the
+// eviction's hipFree is never under running work.
+int epoch_cache(gsv_ctx* c, std::unique_lock<std::mutex>& lk, uint64_t epoch, bool test, const EpochSizes& sz,
+                const uint8_t** d_cache) {
+    auto find = [&]() {
+        for (auto it = c->ethash_caches.begin(); it != c->ethash_caches.end(); ++it)
+            if (it->epoch == epoch && it->test == test) {
+                c->ethash_caches.splice(c->ethash_caches.begin(), c->ethash_caches, it);  // most recently used
+                return true;
+            }
+        return false;
+    };
+    if (!find()) {
+        lk.unlock();
+        std::vector<uint8_t> host(sz.cache_bytes);
+        uint8_t seed[32];
+        eth::seed_hash(epoch * eth::EPOCH_LENGTH, seed);
+        const bool made = eth::make_cache(seed, sz.cache_bytes, host.data());
+        lk.lock();
+        if (!made) return GSV_E_INVALID_ARG;
+        HIPCHK(hipSetDevice(c->device));
+        if (!find()) {
+            while (c->ethash_caches.size() >= GSV_ETHASH_MAX_CACHES) {
+                hipFree(c->ethash_caches.back().d);
+                c->ethash_caches.pop_back();
+            }
+            uint8_t* d = nullptr;
+            if (hipMalloc(&d, sz.cache_bytes) != hipSuccess) return GSV_E_NOMEM;
+            if (hipMemcpy(d, host.data(), sz.cache_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+                hipFree(d);
+                return GSV_E_HIP;
+            }
+            c->ethash_caches.push_front({epoch, test, d, sz.cache_bytes});
+        }
+    }
+    *d_cache = c->ethash_caches.front().d;
+    return GSV_SUCCESS;
+}
+
+// light: a / b are the outputs (mix digest, result); verify: the inputs (mix digest, difficulty)
+int host_batch(gsv_ctx* c, const uint64_t* number, bool test, const uint8_t* hash32, const uint64_t* nonce, size_t n,
+               bool verify, const uint8_t* a_in, const uint8_t* b_in, uint8_t* a_out, uint8_t* b_out,
+               uint8_t* status) {
+    if (!c || n > MAX_N) return GSV_E_INVALID_ARG;
+    if (n == 0) return GSV_SUCCESS;
+    if (!number || !hash32 || !nonce) return GSV_E_INVALID_ARG;
+    if (verify ? (!a_in || !b_in || !status) : (!a_out || !b_out)) return GSV_E_INVALID_ARG;
+    std::map<uint64_t, std::vector<uint32_t>> groups;
+    for (size_t i = 0; i < n; i++) {
+        const uint64_t epoch = number[i] / eth::EPOCH_LENGTH;
+        if (!test && epoch >= MAX_EPOCH) return GSV_E_TOO_LARGE;
+        groups[epoch].push_back((uint32_t)i);
+    }
+    std::vector<uint8_t> h, a, b, st;
+    std::vector<uint64_t> nn;
+    std::unique_lock<std::mutex> lk(c->mu);
+    for (const auto& g : groups) {
+        const std::vector<uint32_t>& items = g.second;
+        const size_t m = items.size();
+        const EpochSizes sz = epoch_sizes(g.first, test);
+        const uint8_t* d_cache = nullptr;
+        int rc = epoch_cache(c, lk, g.first, test, sz, &d_cache);
+        if (rc) return rc;
+        HIPCHK(hipSetDevice(c->device));
+        h.resize(m * 32);
+        nn.resize(m);
+        a.resize(m * 32);
+        b.resize(m * 32);
+        st.resize(m);
+        for (size_t k = 0; k < m; k++) {
+            const size_t i = items[k];
+            memcpy(&h[k * 32], hash32 + i * 32, 32);
+            nn[k] = nonce[i];
+            if (verify) {
+                memcpy(&a[k * 32], a_in + i * 32, 32);
+                memcpy(&b[k * 32], b_in + i * 32, 32);
+            }
+        }
+        Layout L;
+        const EthashStage p(L, m, verify);
+        rc = arena_reserve(c, L.n);
+        if (rc) return rc;
+        uint8_t *d_h = p.hash(c->arena), *d_a = p.a(c->arena), *d_b = p.b(c->arena), *d_st = p.st(c->arena);
+        uint64_t* d_n = p.nonce(c->arena);
+        HIPCHK(hipMemcpyAsync(d_h, h.data(), m * 32, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(d_n, nn.data(), m * 8, hipMemcpyHostToDevice, c->stream));
+        if (verify) {
+            HIPCHK(hipMemcpyAsync(d_a, a.data(), m * 32, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(d_b, b.data(), m * 32, hipMemcpyHostToDevice, c->stream));
+            rc = gsv_ethash_verify_seal_batch_dev(c, d_cache, sz.cache_bytes, sz.dataset_bytes, d_h, d_n, d_a, d_b, m,
+                                                  d_st, c->stream);
+            if (rc) return rc;
+            HIPCHK(hipMemcpyAsync(st.data(), d_st, m, hipMemcpyDeviceToHost, c->stream));
+        } else {
+            rc = gsv_ethash_light_batch_dev(c, d_cache, sz.cache_bytes, sz.dataset_bytes, d_h, d_n, m, d_a, d_b,
+                                            c->stream);
+            if (rc) return rc;
+            HIPCHK(hipMemcpyAsync(a.data(), d_a, m * 32, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(b.data(), d_b, m * 32, hipMemcpyDeviceToHost, c->stream));
+        }
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (size_t k = 0; k < m; k++) {
+            const size_t i = items[k];
+            if (verify) {
+                status[i] = st[k];
+            } else {
+                memcpy(a_out + i * 32, &a[k * 32], 32);
+                memcpy(b_out + i * 32, &b[k * 32], 32);
+            }
+        }
+    }
+    return GSV_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gsv_ethash_dataset_items_dev(gsv_ctx* c, const uint8_t* d_cache, uint64_t cache_bytes, uint64_t first,
+                                 uint64_t count, uint8_t* d_out64, void* stream) {
+    if (!c || !cache_ok(d_cache, cache_bytes) || first > (1ull << 32) || count > (1ull << 32) - first)
+        return GSV_E_INVALID_ARG;
+    if (count == 0) return GSV_SUCCESS;
+    if (!d_out64 || ((uintptr_t)d_out64 & 15) || count > 0xFFFFFFFFull) return GSV_E_INVALID_ARG;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    KTimer t(c, GSV_K_ETHASH_ITEMS, st);
+    return hip_err(gsv::launch_ethash_items(d_cache, cache_bytes, (uint32_t)first, (uint32_t)count, d_out64, st));
+}
+
+int gsv_ethash_light_batch_dev(gsv_ctx* c, const uint8_t* d_cache, uint64_t cache_bytes, uint64_t dataset_bytes,
+                               const uint8_t* d_hash32, const uint64_t* d_nonce, size_t n, uint8_t* d_mix32,
+                               uint8_t* d_result32, void* stream) {
+    if (!c || !cache_ok(d_cache, cache_bytes) || !dataset_ok(dataset_bytes) || n > MAX_N) return GSV_E_INVALID_ARG;
+    if (n == 0) return GSV_SUCCESS;
+    if (!seed_ok(d_hash32, d_nonce) || !d_mix32 || !d_result32) return GSV_E_INVALID_ARG;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    KTimer t(c, GSV_K_ETHASH_LIGHT, st);
+    return hip_err(gsv::launch_ethash_light(d_cache, cache_bytes, dataset_bytes, d_hash32, d_nonce, (uint32_t)n,
+                                            d_mix32, d_result32, st));
+}
+
+int gsv_ethash_verify_seal_batch_dev(gsv_ctx* c, const uint8_t* d_cache, uint64_t cache_bytes, uint64_t dataset_bytes,
+                                     const uint8_t* d_hash32, const uint64_t* d_nonce, const uint8_t* d_mix32,
+                                     const uint8_t* d_difficulty32, size_t n, uint8_t* d_status, void* stream) {
+    if (!c || !cache_ok(d_cache, cache_bytes) || !dataset_ok(dataset_bytes) || n > MAX_N) return GSV_E_INVALID_ARG;
+    if (n == 0) return GSV_SUCCESS;
+    if (!seed_ok(d_hash32, d_nonce) || !d_mix32 || !d_difficulty32 || !d_status) return GSV_E_INVALID_ARG;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    KTimer t(c, GSV_K_ETHASH_LIGHT, st);
+    return hip_err(gsv::launch_ethash_verify(d_cache, cache_bytes, dataset_bytes, d_hash32, d_nonce, d_mix32,
+                                             d_difficulty32, (uint32_t)n, d_status, st));
+}
+
+int gsv_ethash_light_batch(gsv_ctx* c, const uint64_t* number, int test_mode, const uint8_t* hash32,
+                           const uint64_t* nonce, size_t n, uint8_t* mix32_out, uint8_t* result32_out) {
+    return host_batch(c, number, test_mode != 0, hash32, nonce, n, false, nullptr, nullptr, mix32_out, result32_out,
+                      nullptr);
+}
+
+int gsv_ethash_verify_seal_batch(gsv_ctx* c, const uint64_t* number, const uint8_t* hash32, const uint64_t* nonce,
+                                 const uint8_t* mix32, const uint8_t* difficulty32, size_t n, int test_mode,
+                                 uint8_t* status) {
+    return host_batch(c, number, test_mode != 0, hash32, nonce, n, true, mix32, difficulty32, nullptr, nullptr,
+                      status);
+}
+
+int gsv_ctx_ethash_caches(gsv_ctx* c, size_t* count) {
+    if (!c || !count) return GSV_E_INVALID_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    *count = c->ethash_caches.size();
+    return GSV_SUCCESS;
+}
+
+}  // extern "C"

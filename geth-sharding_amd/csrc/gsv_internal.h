@@ -150,6 +150,18 @@ hipError_t launch_bn256_g1_mul(const uint8_t* d_in96, uint32_t n, uint8_t* d_out
 hipError_t launch_modexp(const uint8_t* d_in, uint32_t n, uint32_t bl, uint32_t el, uint32_t ml, uint8_t* d_out,
                          uint8_t* d_work, hipStream_t st);
 
+// ethash.hip: dataset items [first, first + count), hashimotoLight and VerifySeal over a device-resident cache
+// of cache_bytes (a multiple of 64, 16-byte aligned) and a dataset of dataset_bytes (a multiple of 128, at
+// most 2^38); hash rows 4-byte and nonces 8-byte aligned, d_out64 16-byte aligned
+hipError_t launch_ethash_items(const uint8_t* d_cache, uint64_t cache_bytes, uint32_t first, uint32_t count,
+                               uint8_t* d_out64, hipStream_t st);
+hipError_t launch_ethash_light(const uint8_t* d_cache, uint64_t cache_bytes, uint64_t dataset_bytes,
+                               const uint8_t* d_hash32, const uint64_t* d_nonce, uint32_t n, uint8_t* d_mix32,
+                               uint8_t* d_result32, hipStream_t st);
+hipError_t launch_ethash_verify(const uint8_t* d_cache, uint64_t cache_bytes, uint64_t dataset_bytes,
+                                const uint8_t* d_hash32, const uint64_t* d_nonce, const uint8_t* d_mix32,
+                                const uint8_t* d_difficulty32, uint32_t n, uint8_t* d_status, hipStream_t st);
+
 // collation.hip: CollationHeader.Hash() with ProposerSignature empty (k_header_hash alone: the hash the
 // proposer signs), no nil fields
 hipError_t launch_header_hash_unsigned(const uint8_t* d_sid32, const uint8_t* d_root32, const uint8_t* d_per32,

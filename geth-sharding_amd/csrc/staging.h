@@ -250,6 +250,16 @@ struct HeaderStage {  // gsv_collation_header_verify_batch
           nil(L.buf(n, has_nil)), hash(L.buf(n * 32, want_hash)), signer(L.buf(n * 20, want_signer)), st(L.buf(n)),
           scr(L.buf(scratch_bytes)) {}
 };
+// gsv_ethash_light_batch / gsv_ethash_verify_seal_batch, one epoch's items: a and b are the two 32-byte
+// outputs (mix digest, result) or the two 32-byte inputs (mix digest, difficulty) of the verify form
+struct EthashStage {
+    B8 hash;
+    Buf<uint64_t> nonce;
+    B8 a, b, st;
+    EthashStage(Layout& L, size_t n, bool verify)
+        : hash(L.buf(n * 32)), nonce(L.buf<uint64_t>(n * 8)), a(L.buf(n * 32)), b(L.buf(n * 32)),
+          st(L.buf(n, verify)) {}
+};
 
 }  // namespace api
 }  // namespace gsv

@@ -1068,6 +1068,95 @@ def _modexp_batch_dev(self, in_t, base_len: int, exp_len: int, mod_len: int, out
                                            _tptr(out_t), _tptr(work_t), sp))
 
 
+def _rows32(a) -> np.ndarray:
+    """(n, 32) uint8 from an array, one bytes object, or a sequence of 32-byte strings"""
+    if isinstance(a, (list, tuple)) and (not a or isinstance(a[0], (bytes, bytearray, memoryview))):
+        a = b"".join(bytes(x) for x in a)
+    a = np.ascontiguousarray(_np_u8(a)).reshape(-1, 32)
+    return a if a.flags.writeable else a.copy()  # torch.from_numpy wants a writable array
+
+
+def _ethash_rows(hashes, nonces):
+    h = _rows32(hashes)
+    nn = np.ascontiguousarray(nonces, np.uint64).reshape(-1)
+    if h.shape[0] != nn.shape[0]:
+        raise ValueError("ethash: one 32-byte hash and one nonce per item")
+    return h, nn
+
+
+def _ethash_light_batch(self, numbers, hashes, nonces, test_mode=False):
+    """hashimotoLight per (block number, hash without nonce, nonce) (gsv.h gsv_ethash_light_batch): items are
+    grouped by epoch, the epoch caches are made on the host and kept on the device.  Returns (mix digests
+    (n, 32), results (n, 32)) in input order."""
+    h, nn = _ethash_rows(hashes, nonces)
+    num = np.ascontiguousarray(numbers, np.uint64).reshape(-1)
+    n = h.shape[0]
+    if num.shape[0] != n:
+        raise ValueError("ethash: one block number per item")
+    mix = np.zeros((n, 32), np.uint8)
+    res = np.zeros((n, 32), np.uint8)
+    check(_lib.load().gsv_ethash_light_batch(self._h, _ptr(num), int(bool(test_mode)), _ptr(h), _ptr(nn), n, _ptr(mix),
+                                             _ptr(res)))
+    return mix, res
+
+
+def _ethash_verify_seal_batch(self, numbers, hashes, nonces, mixes, difficulties, test_mode=False):
+    """VerifySeal's checks per item (gsv.h gsv_ethash_verify_seal_batch): mixes (n, 32), difficulties (n, 32)
+    big-endian.  Returns status (n,) uint8: ST_OK, ST_INVALID_DIFFICULTY, ST_INVALID_MIX_DIGEST, ST_INVALID_POW."""
+    h, nn = _ethash_rows(hashes, nonces)
+    num = np.ascontiguousarray(numbers, np.uint64).reshape(-1)
+    mix = _rows32(mixes)
+    dif = _rows32(difficulties)
+    n = h.shape[0]
+    if num.shape[0] != n or mix.shape[0] != n or dif.shape[0] != n:
+        raise ValueError("ethash: one block number, mix digest and difficulty per item")
+    st = np.zeros(n, np.uint8)
+    check(_lib.load().gsv_ethash_verify_seal_batch(self._h, _ptr(num), _ptr(h), _ptr(nn), _ptr(mix), _ptr(dif), n,
+                                                   int(bool(test_mode)), _ptr(st)))
+    return st
+
+
+def _ethash_cache_bytes(cache_t) -> int:
+    if not cache_t.is_contiguous():
+        raise ValueError("ethash: the cache is a contiguous tensor of gsv_ethash_make_cache's bytes")
+    return cache_t.numel() * cache_t.element_size()
+
+
+def _ethash_dataset_items_dev(self, cache_t, first: int, count: int, out_t, stream=None):
+    """torch CUDA tensors: cache_t the verification cache's bytes (16-byte aligned), out_t (count, 64) uint8.
+    Dataset items [first, first + count).  Only enqueues on `stream`: one launch, no allocation."""
+    if out_t is not None and (not out_t.is_contiguous() or out_t.numel() * out_t.element_size() < 64 * int(count)):
+        raise ValueError("ethash: out_t holds count rows of 64 bytes")
+    check(_lib.load().gsv_ethash_dataset_items_dev(self._h, _tptr(cache_t), _ethash_cache_bytes(cache_t), int(first),
+                                                   int(count), _tptr(out_t), _sp(stream)))
+
+
+def _ethash_light_batch_dev(self, cache_t, dataset_bytes: int, hash_t, nonce_t, mix_t, result_t, stream=None, n=None):
+    """torch CUDA tensors: hash_t n rows of 32 bytes (4-byte aligned), nonce_t n int64 / uint64 values (the
+    nonce as a number), mix_t and result_t n rows of 32 bytes (any alignment).  Only enqueues on `stream`."""
+    n = int(nonce_t.numel()) if n is None else int(n)
+    check(_lib.load().gsv_ethash_light_batch_dev(self._h, _tptr(cache_t), _ethash_cache_bytes(cache_t),
+                                                 int(dataset_bytes), _tptr(hash_t), _tptr(nonce_t), n, _tptr(mix_t),
+                                                 _tptr(result_t), _sp(stream)))
+
+
+def _ethash_verify_seal_batch_dev(self, cache_t, dataset_bytes: int, hash_t, nonce_t, mix_t, difficulty_t, status_t,
+                                  stream=None, n=None):
+    """As ethash_light_batch_dev, with the headers' mix digests and 32-byte big-endian difficulties in and one
+    status byte per item out."""
+    n = int(nonce_t.numel()) if n is None else int(n)
+    check(_lib.load().gsv_ethash_verify_seal_batch_dev(self._h, _tptr(cache_t), _ethash_cache_bytes(cache_t),
+                                                       int(dataset_bytes), _tptr(hash_t), _tptr(nonce_t), _tptr(mix_t),
+                                                       _tptr(difficulty_t), n, _tptr(status_t), _sp(stream)))
+
+
+def _ethash_caches(self) -> int:
+    """epoch caches the context holds for the ethash host forms (at most _lib.ETHASH_MAX_CACHES)"""
+    cnt = ctypes.c_size_t()
+    check(_lib.load().gsv_ctx_ethash_caches(self._h, ctypes.byref(cnt)))
+    return cnt.value
+
+
 def _arena_read(self, off, n):
     """Test hook (gsv.h gsv_ctx_arena_read): n bytes of the staging arena from `off`, as they are now."""
     out = np.zeros(n, np.uint8)
@@ -1102,6 +1191,12 @@ Context.ecies_decrypt_batch = _ecies_decrypt_batch
 Context.ecies_encrypt_batch = _ecies_encrypt_batch
 Context.ecies_decrypt_batch_dev = _ecies_decrypt_batch_dev
 Context.ecies_encrypt_batch_dev = _ecies_encrypt_batch_dev
+Context.ethash_light_batch = _ethash_light_batch
+Context.ethash_verify_seal_batch = _ethash_verify_seal_batch
+Context.ethash_dataset_items_dev = _ethash_dataset_items_dev
+Context.ethash_light_batch_dev = _ethash_light_batch_dev
+Context.ethash_verify_seal_batch_dev = _ethash_verify_seal_batch_dev
+Context.ethash_caches = _ethash_caches
 Context.modexp_batch = _modexp_batch
 Context.modexp_batch_dev = _modexp_batch_dev
 Context._arena_read = _arena_read

@@ -30,6 +30,9 @@ ST_INVALID_CURVE = 12
 ST_BODY_TOO_LARGE = 13
 ST_INVALID_MESSAGE = 14
 ST_MODEXP_TOO_LONG = 15
+ST_INVALID_DIFFICULTY = 16
+ST_INVALID_MIX_DIGEST = 17
+ST_INVALID_POW = 18
 
 # a short text per per-item status: the reference's error string where it has one (include/gsv.h names
 # the sources)
@@ -50,6 +53,9 @@ STATUS_STRINGS = {
     ST_BODY_TOO_LARGE: "serialized body size exceeds the collation size limit",
     ST_INVALID_MESSAGE: "ecies: invalid message",
     ST_MODEXP_TOO_LONG: "modexp: a length above GSV_MODEXP_MAX_LEN",
+    ST_INVALID_DIFFICULTY: "non-positive difficulty",
+    ST_INVALID_MIX_DIGEST: "invalid mix digest",
+    ST_INVALID_POW: "invalid proof-of-work",
 }
 
 SIGNER_EIP155 = 0
@@ -78,6 +84,11 @@ K_TX_SEAL = 14
 K_MODEXP = 15
 K_SHA256 = 16
 K_RIPEMD160 = 17
+K_ETHASH_ITEMS = 18
+K_ETHASH_LIGHT = 19
+K_TOP = 20  # GSV_K_TOP: gsv_ctx_kernel_time takes every id below it
+
+ETHASH_MAX_CACHES = 3  # GSV_ETHASH_MAX_CACHES: epoch caches a context keeps for the ethash host forms
 
 MODEXP_MAX_LEN = 1024  # GSV_MODEXP_MAX_LEN: the cap on baseLen, expLen and modLen of the modexp precompile
 
@@ -104,6 +115,7 @@ _u32p = ctypes.POINTER(ctypes.c_uint32)
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _vp = ctypes.c_void_p
 _sz = ctypes.c_size_t
+_u64 = ctypes.c_uint64
 
 # (name, restype, argtypes) for every symbol declared in include/gsv.h
 SIGNATURES = [
@@ -184,6 +196,16 @@ SIGNATURES = [
     ("gsv_modexp_work_bytes", _sz, [_sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
     ("gsv_modexp_batch_dev", ctypes.c_int, [_vp, _vp, _sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp,
                                             _vp]),
+    ("gsv_ethash_cache_size", _u64, [_u64]),
+    ("gsv_ethash_dataset_size", _u64, [_u64]),
+    ("gsv_ethash_seed_hash", ctypes.c_int, [_u64, _vp]),
+    ("gsv_ethash_make_cache", ctypes.c_int, [_vp, _u64, _vp]),
+    ("gsv_ethash_dataset_items_dev", ctypes.c_int, [_vp, _vp, _u64, _u64, _u64, _vp, _vp]),
+    ("gsv_ethash_light_batch_dev", ctypes.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _sz, _vp, _vp, _vp]),
+    ("gsv_ethash_verify_seal_batch_dev", ctypes.c_int, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    ("gsv_ethash_light_batch", ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, _sz, _vp, _vp]),
+    ("gsv_ethash_verify_seal_batch", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_int, _vp]),
+    ("gsv_ctx_ethash_caches", ctypes.c_int, [_vp, ctypes.POINTER(_sz)]),
     ("gsv_chunk_root_prepare", ctypes.c_int, [_vp, _vp, _sz]),
     ("gsv_bn256_pairing_prepare", ctypes.c_int, [_vp, _vp, _sz]),
     ("gsv_notary_prepare", ctypes.c_int, [_vp, _vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_uint32]),

@@ -1,0 +1,159 @@
+"""Mirror of the reference's consensus/ethash, the part a light verifier runs, batched on the GPU.
+
+    cacheSize(block), datasetSize(block)   algorithm.go:53-91 (the formula; the tables hold its values)
+    seedHash(block)                        algorithm.go:110-120
+    generateCache(size, seed)              algorithm.go:128-197, on the host (include/gsv.h says why)
+    generateDatasetItems(cache, first, count)   generateDatasetItem over a range: the body of generateDataset
+    hashimotoLight(size, cache, hash, nonce)    algorithm.go:375 -> (digest, result)
+    hashimotoLightBatch(size, cache, hashes, nonces)
+    Ethash(test_mode).VerifySeal / VerifySeals  consensus.go:463-501, by block number
+
+The nonce is the number (Header.Nonce.Uint64()); types.BlockNonce is its big-endian bytes.  Not here:
+Header.HashNoNonce() from the header's RLP (Context.keccak256_batch makes it), the rest of verifyHeader,
+hashimotoFull, the sealer and cache files on disk.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _lib, _np_u8, _ptr, _rows32, default_context
+from ._lib import check
+
+epochLength = 30000
+MAX_UINT256 = (1 << 256) - 1
+
+
+class ErrInvalidDifficulty(ValueError):
+    """errInvalidDifficulty (consensus.go:56)"""
+
+
+class ErrInvalidMixDigest(ValueError):
+    """errInvalidMixDigest (consensus.go:57)"""
+
+
+class ErrInvalidPoW(ValueError):
+    """errInvalidPoW (consensus.go:58)"""
+
+
+_ERRORS = {_lib.ST_INVALID_DIFFICULTY: ErrInvalidDifficulty, _lib.ST_INVALID_MIX_DIGEST: ErrInvalidMixDigest,
+           _lib.ST_INVALID_POW: ErrInvalidPoW}
+
+
+def cacheSize(block: int) -> int:
+    return int(_lib.load().gsv_ethash_cache_size(int(block)))
+
+
+def datasetSize(block: int) -> int:
+    return int(_lib.load().gsv_ethash_dataset_size(int(block)))
+
+
+def seedHash(block: int) -> bytes:
+    out = np.zeros(32, np.uint8)
+    check(_lib.load().gsv_ethash_seed_hash(int(block), _ptr(out)))
+    return out.tobytes()
+
+
+def generateCache(size: int, seed: bytes) -> np.ndarray:
+    """the verification cache of `size` bytes for `seed`, as uint8 (the reference's words, little-endian)"""
+    seed = _np_u8(seed)
+    if seed.shape != (32,):
+        raise ValueError("ethash: the seed is 32 bytes")
+    out = np.zeros(int(size), np.uint8)
+    check(_lib.load().gsv_ethash_make_cache(_ptr(seed), int(size), _ptr(out)))
+    return out
+
+
+def _device_cache(cache, ctx):
+    """the cache as a CUDA uint8 tensor on the context's device (a tensor already there is used as it is)"""
+    import torch
+    if isinstance(cache, torch.Tensor):
+        return cache
+    return torch.from_numpy(np.ascontiguousarray(_np_u8(cache))).to(f"cuda:{ctx.device}")
+
+
+def generateDatasetItems(cache, first: int, count: int, ctx=None) -> np.ndarray:
+    """dataset items [first, first + count) as (count, 64) uint8"""
+    import torch
+    ctx = ctx or default_context()
+    d_cache = _device_cache(cache, ctx)
+    out = torch.empty((int(count), 64), dtype=torch.uint8, device=d_cache.device)
+    ctx.ethash_dataset_items_dev(d_cache, first, count, out)
+    torch.cuda.synchronize(d_cache.device)
+    return out.cpu().numpy()
+
+
+def hashimotoLightBatch(size: int, cache, hashes, nonces, ctx=None):
+    """(digests (n, 32), results (n, 32)) of hashimotoLight(size, cache, hashes[i], nonces[i])"""
+    import torch
+    ctx = ctx or default_context()
+    d_cache = _device_cache(cache, ctx)
+    h = _rows32(hashes)
+    nn = np.ascontiguousarray(nonces, np.uint64).reshape(-1)
+    n = h.shape[0]
+    if nn.shape[0] != n:
+        raise ValueError("ethash: one 32-byte hash and one nonce per item")
+    dev = d_cache.device
+    d_h = torch.from_numpy(h).to(dev)
+    d_n = torch.from_numpy(nn.view(np.int64)).to(dev)
+    d_mix = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+    d_res = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+    ctx.ethash_light_batch_dev(d_cache, size, d_h, d_n, d_mix, d_res, n=n)
+    torch.cuda.synchronize(dev)
+    return d_mix.cpu().numpy(), d_res.cpu().numpy()
+
+
+def hashimotoLight(size: int, cache, hash: bytes, nonce: int, ctx=None):
+    mix, res = hashimotoLightBatch(size, cache, [bytes(hash)], [int(nonce)], ctx)
+    return mix[0].tobytes(), res[0].tobytes()
+
+
+def _difficulty_rows(difficulties) -> np.ndarray:
+    """32 bytes big-endian per difficulty.  Negative means non-positive (row of zeros: ErrInvalidDifficulty);
+    2^256 and more cannot be written in 32 bytes and is handled by the caller."""
+    rows = np.zeros((len(difficulties), 32), np.uint8)
+    for i, d in enumerate(difficulties):
+        d = int(d)
+        if 0 < d <= MAX_UINT256:
+            rows[i] = np.frombuffer(d.to_bytes(32, "big"), np.uint8)
+    return rows
+
+
+class Ethash:
+    """consensus.Engine's seal check.  test_mode is the reference's ModeTest: a 1,024-byte cache, still seeded
+    by the epoch, and a 32 KiB dataset."""
+
+    def __init__(self, test_mode: bool = False, ctx=None):
+        self.test_mode = bool(test_mode)
+        self.ctx = ctx or default_context()
+
+    def hashimotoLight(self, numbers, hashes, nonces):
+        return self.ctx.ethash_light_batch(numbers, hashes, nonces, self.test_mode)
+
+    def VerifySeals(self, numbers, hashes_no_nonce, nonces, mix_digests, difficulties) -> np.ndarray:
+        """status (n,) uint8 per header: ST_OK, ST_INVALID_DIFFICULTY, ST_INVALID_MIX_DIGEST or ST_INVALID_POW.
+        difficulties: Python ints, or (n, 32) big-endian rows."""
+        if isinstance(difficulties, np.ndarray) and difficulties.dtype == np.uint8:
+            return self.ctx.ethash_verify_seal_batch(numbers, hashes_no_nonce, nonces, mix_digests, difficulties,
+                                                     self.test_mode)
+        difficulties = [int(d) for d in difficulties]
+        # A difficulty of 2^256 or more has target floor((2^256 - 1) / d) = 0: only a zero result passes.  The
+        # library sees it as difficulty 2^256 - 1 (target 1: mix and difficulty checks as ever), and a result
+        # of exactly one is failed here.
+        big = [i for i, d in enumerate(difficulties) if d > MAX_UINT256]
+        rows = _difficulty_rows([MAX_UINT256 if d > MAX_UINT256 else d for d in difficulties])
+        st = self.ctx.ethash_verify_seal_batch(numbers, hashes_no_nonce, nonces, mix_digests, rows, self.test_mode)
+        ok_big = [i for i in big if st[i] == _lib.ST_OK]
+        if ok_big:
+            num = np.ascontiguousarray(numbers, np.uint64).reshape(-1)[ok_big]
+            h = _rows32(hashes_no_nonce)[ok_big]
+            nn = np.ascontiguousarray(nonces, np.uint64).reshape(-1)[ok_big]
+            _, res = self.ctx.ethash_light_batch(num, h, nn, self.test_mode)
+            for k, i in enumerate(ok_big):
+                if res[k].any():
+                    st[i] = _lib.ST_INVALID_POW
+        return st
+
+    def VerifySeal(self, number: int, hash_no_nonce: bytes, nonce: int, mix_digest: bytes, difficulty: int) -> None:
+        st = int(self.VerifySeals([number], [bytes(hash_no_nonce)], [nonce], [bytes(mix_digest)], [difficulty])[0])
+        if st != _lib.ST_OK:
+            raise _ERRORS[st](_lib.STATUS_STRINGS[st])

@@ -129,6 +129,9 @@ extern "C" {
 #define GSV_ST_BODY_TOO_LARGE 13   /* SerializeTxToBlob's size error   sharding/collation.go:169-171 */
 #define GSV_ST_INVALID_MESSAGE 14  /* ecies.ErrInvalidMessage          ecies/ecies.go:143 */
 #define GSV_ST_MODEXP_TOO_LONG 15  /* a modexp length above GSV_MODEXP_MAX_LEN: not the reference's, see there */
+#define GSV_ST_INVALID_DIFFICULTY 16 /* ethash errInvalidDifficulty    consensus/ethash/consensus.go:56 */
+#define GSV_ST_INVALID_MIX_DIGEST 17 /* ethash errInvalidMixDigest     consensus/ethash/consensus.go:57 */
+#define GSV_ST_INVALID_POW 18        /* ethash errInvalidPoW           consensus/ethash/consensus.go:58 */
 
 /* signer kinds for gsv_tx_sender_batch and gsv_tx_sign_batch (core/types/transaction_signing.go) */
 #define GSV_SIGNER_EIP155 0
@@ -186,6 +189,11 @@ int gsv_ctx_set_timing(gsv_ctx *ctx, int enable);
 #define GSV_K_SHA256 16     /* the sha256hash precompile: one launch per call */
 #define GSV_K_RIPEMD160 17  /* the ripemd160hash precompile: one launch per call */
 #define GSV_K_CAP 18
+/* Ids added behind GSV_K_CAP (pinned like the four before it); gsv_ctx_kernel_time takes every id below
+ * GSV_K_TOP. */
+#define GSV_K_ETHASH_ITEMS 18 /* ethash dataset items: one launch per call */
+#define GSV_K_ETHASH_LIGHT 19 /* ethash hashimotoLight / VerifySeal: one launch per call */
+#define GSV_K_TOP 20
 /* total milliseconds and launch count accumulated for kernel `kid` since the last reset */
 int gsv_ctx_kernel_time(gsv_ctx *ctx, int kid, double *total_ms, long *launches);
 int gsv_ctx_reset_timing(gsv_ctx *ctx);
@@ -617,6 +625,65 @@ int gsv_modexp_batch(gsv_ctx *ctx, const uint8_t *in, const uint64_t *off, size_
 size_t gsv_modexp_work_bytes(size_t n, uint32_t base_len, uint32_t exp_len, uint32_t mod_len);
 int gsv_modexp_batch_dev(gsv_ctx *ctx, const uint8_t *d_in, size_t n, uint32_t base_len, uint32_t exp_len,
                          uint32_t mod_len, uint8_t *d_out, uint8_t *d_work, void *stream);
+
+/* ---- ethash (consensus/ethash): hashimotoLight, VerifySeal, dataset items ----
+ * What Ethash.VerifyHeaders (consensus.go:90) spends its time in: VerifySeal (consensus.go:463-501) runs
+ * hashimotoLight (algorithm.go:375) per header over the epoch's verification cache.  An epoch is 30,000
+ * blocks.  Not here: Header.HashNoNonce() from the header's RLP (callers pass the 32-byte hash;
+ * gsv_keccak256_batch makes it from the 13-field RLP), the rest of verifyHeader (timestamps, gas limits,
+ * CalcDifficulty), hashimotoFull with full-DAG storage and the sealer, and cache files on disk.
+ *
+ * Host only, no context: cacheSize / datasetSize (algorithm.go:53-91) by the reference's formula for every
+ * epoch (its 2,048-entry tables hold the same values), seedHash (algorithm.go:110-120) and generateCache
+ * (algorithm.go:128-197) over cache_bytes, a multiple of 64 of at least 64 (else GSV_E_INVALID_ARG): the
+ * bytes of the reference's cache on a little-endian machine, which is what the device forms read.  The
+ * epoch-0 cache is 1.05 million strictly dependent permutations, under a second on one core. */
+uint64_t gsv_ethash_cache_size(uint64_t block);
+uint64_t gsv_ethash_dataset_size(uint64_t block);
+int gsv_ethash_seed_hash(uint64_t block, uint8_t *out32);
+int gsv_ethash_make_cache(const uint8_t *seed32, uint64_t cache_bytes, uint8_t *out);
+/* Device-resident.  Each only enqueues one launch (GSV_K_ETHASH_ITEMS / GSV_K_ETHASH_LIGHT) on `stream`
+ * (NULL = the context stream): no allocation, no synchronisation, no prepare call, capturable.  d_cache is
+ * the caller's device copy of a gsv_ethash_make_cache result, 16-byte aligned; one (cache, dataset size)
+ * pair per call.  GSV_E_INVALID_ARG: cache_bytes below 64 or no multiple of 64 (or 2^38 and more);
+ * dataset_bytes below 128, no multiple of 128, or above 2^38 (2 parent + 1 fits 32 bits); a misaligned
+ * buffer; n above 2^31 - 1.  n == 0 (count == 0): success, nothing enqueued.
+ *   items:  d_out64[64 k .. +64) = generateDatasetItem(cache, first + k) (algorithm.go:232-261) for k < count,
+ *           the body of generateDataset; first + count <= 2^32; d_out64 16-byte aligned.
+ *   light:  (d_mix32[32 i .. +32), d_result32[32 i .. +32)) = hashimotoLight(dataset_bytes, cache,
+ *           d_hash32[32 i .. +32), d_nonce[i]).  The nonce is the NUMBER (Header.Nonce.Uint64()): the kernel
+ *           lays it little-endian into the seed; types.BlockNonce is its big-endian bytes.  d_hash32 4-byte
+ *           and d_nonce 8-byte aligned; the outputs may have any byte alignment.
+ *   verify: d_status[i] by VerifySeal's checks in its order (consensus.go:477-499), d_difficulty32 32 bytes
+ *           big-endian, d_mix32 the header's MixDigest, both of any alignment:
+ *             1. difficulty == 0                                    GSV_ST_INVALID_DIFFICULTY
+ *             2. digest != mix                                      GSV_ST_INVALID_MIX_DIGEST
+ *             3. result > floor((2^256 - 1) / difficulty)           GSV_ST_INVALID_POW
+ *             4. else                                               GSV_ST_OK
+ *           (3 is decided by the high half of the 512-bit product result x difficulty: no division.) */
+int gsv_ethash_dataset_items_dev(gsv_ctx *ctx, const uint8_t *d_cache, uint64_t cache_bytes, uint64_t first,
+                                 uint64_t count, uint8_t *d_out64, void *stream);
+int gsv_ethash_light_batch_dev(gsv_ctx *ctx, const uint8_t *d_cache, uint64_t cache_bytes, uint64_t dataset_bytes,
+                               const uint8_t *d_hash32, const uint64_t *d_nonce, size_t n, uint8_t *d_mix32,
+                               uint8_t *d_result32, void *stream);
+int gsv_ethash_verify_seal_batch_dev(gsv_ctx *ctx, const uint8_t *d_cache, uint64_t cache_bytes,
+                                     uint64_t dataset_bytes, const uint8_t *d_hash32, const uint64_t *d_nonce,
+                                     const uint8_t *d_mix32, const uint8_t *d_difficulty32, size_t n,
+                                     uint8_t *d_status, void *stream);
+/* Host forms by block number: number[i] picks item i's epoch (number / 30000).  Items are grouped by epoch
+ * and the results come back in input order.  Per epoch the cache is generated on the host, outside the
+ * context's lock, and uploaded; a context keeps the caches of at most GSV_ETHASH_MAX_CACHES epochs, least
+ * recently used out first, and frees one only inside a host call that has synchronised (never under
+ * running work).  test_mode != 0 is the reference's ModeTest: a 1,024-byte cache, still seeded by the
+ * epoch, and a 32 KiB dataset (ethash.go:219-221, consensus.go:485-487).  gsv_ctx_ethash_caches: how many
+ * caches the context holds now. */
+#define GSV_ETHASH_MAX_CACHES 3
+int gsv_ethash_light_batch(gsv_ctx *ctx, const uint64_t *number, int test_mode, const uint8_t *hash32,
+                           const uint64_t *nonce, size_t n, uint8_t *mix32_out, uint8_t *result32_out);
+int gsv_ethash_verify_seal_batch(gsv_ctx *ctx, const uint64_t *number, const uint8_t *hash32, const uint64_t *nonce,
+                                 const uint8_t *mix32, const uint8_t *difficulty32, size_t n, int test_mode,
+                                 uint8_t *status);
+int gsv_ctx_ethash_caches(gsv_ctx *ctx, size_t *count);
 
 /* ---- synthetic signed workload (bench / test data generator; signing is not on the path) ----
  * key_i, msg_i, nonce_i = Keccak256(le64(seed) || le64(i) || "key"/"msg"/"nce"), key and nonce
