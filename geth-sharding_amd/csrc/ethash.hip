@@ -10,9 +10,16 @@
 //                    The dependent chain of row fetches per lane is half of one lane per header's, and a
 //                    header keeps twice the loads in flight.
 //
+//   k_ethash_full    hashimoto with lookups in the device-resident dataset (hashimotoFull, algorithm.go:393-405),
+//                    EIGHT adjacent lanes per nonce in the access loop, each reading a quarter of the 128-byte
+//                    page (ethash_dev.cuh hashimoto_full); its modes are the plain form, VerifySeal's checks
+//                    and the sealer's finish launch
+//   k_ethash_search  the same body over n headers x span nonces, the inner loop of mine (sealer.go:97-152): a
+//                    winner lowers its header's offset by atomicMin
+//
 // Out of scope here: Header.HashNoNonce() from the header's RLP (callers pass the 32-byte hash;
 // gsv_keccak256_batch makes it from the 13-field RLP), the rest of verifyHeader (timestamps, gas limits,
-// CalcDifficulty), hashimotoFull with full-DAG storage and the sealer, and cache files on disk.
+// CalcDifficulty), DAG and cache files on disk, remote mining / GetWork, and pre-generating the next epoch.
 #include "ethash_dev.cuh"
 #include "ethash_host.h"
 #include "gsv_internal.h"
@@ -117,6 +124,103 @@ __global__ __launch_bounds__(256) void k_ethash_light(Cache cache, ModRecip page
     }
 }
 
+// One item per lane, every lane of the workgroup in the body: an item past the batch's end computes the last
+// item again and writes nothing.  FM_FULL writes mix_out / result_out; FM_VERIFY reads mix_in / difficulty and
+// writes status (the light kernel's checks, in its order); FM_FINISH is the sealer's last launch: item h is
+// nonce start[h] + offset[h] when the search left an offset, and it writes nonce_out / mix_out / result_out /
+// found, zeros where nothing was found.
+enum FullMode { FM_FULL = 0, FM_VERIFY = 1, FM_FINISH = 2 };
+
+template <int MODE>
+__global__ __launch_bounds__(FULL_THREADS) void k_ethash_full(Dataset ds, const uint32_t* __restrict__ hash32,
+                                                              const uint64_t* __restrict__ nonce, uint32_t n,
+                                                              uint8_t* __restrict__ mix_out,
+                                                              uint8_t* __restrict__ result_out,
+                                                              const uint8_t* __restrict__ mix_in,
+                                                              const uint8_t* __restrict__ difficulty,
+                                                              uint8_t* __restrict__ status,
+                                                              const uint32_t* __restrict__ offset,
+                                                              uint64_t* __restrict__ nonce_out) {
+    __shared__ FullShared sh;
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = t < n;
+    const uint32_t h = live ? t : n - 1;
+    uint32_t hw[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) hw[k] = hash32[(size_t)h * 8 + k];
+    uint64_t nn = nonce[h];
+    uint32_t off = 0;
+    if constexpr (MODE == FM_FINISH) {
+        off = offset[h];
+        nn += off;  // mod 2^64, as the reference's nonce++
+        // a header with no winner (off = 0xFFFFFFFF) runs the body on that nonce all the same: the body's
+        // __syncthreads() takes every lane through it, and its rows are zeroed below
+    }
+    uint32_t digest[8], result[8];
+    hashimoto_full(digest, result, ds, hw, nn, sh);
+    if (!live) return;
+
+    if constexpr (MODE == FM_FULL) {
+        store_row32(mix_out, h, digest);
+        store_row32(result_out, h, result);
+    } else if constexpr (MODE == FM_FINISH) {
+        const bool found = off != 0xFFFFFFFFu;
+        if (!found) {
+            nn = 0;
+#pragma unroll
+            for (int k = 0; k < 8; k++) digest[k] = result[k] = 0;
+        }
+        // nonce_out is 8-byte aligned (checked on the host); the rows may not be
+        nonce_out[h] = nn;
+        store_row32(mix_out, h, digest);
+        store_row32(result_out, h, result);
+        status[h] = found ? 1 : 0;
+    } else {
+        // the reference's order (consensus.go:477-499)
+        uint32_t d[8], want[8];
+        load_row32(d, difficulty, h);
+        load_row32(want, mix_in, h);
+        uint32_t dnz = 0, diff = 0;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            dnz |= d[k];
+            diff |= want[k] ^ digest[k];
+        }
+        uint8_t st = GSV_ST_OK;
+        if (dnz == 0) st = GSV_ST_INVALID_DIFFICULTY;
+        else if (diff != 0) st = GSV_ST_INVALID_MIX_DIGEST;
+        else if (pow_exceeds_target(result, d)) st = GSV_ST_INVALID_POW;
+        status[h] = st;
+    }
+}
+
+// n headers x span nonces.  A header takes blocks_per_header = ceil(span / 256) consecutive workgroups, so the
+// header of a workgroup is uniform; item k of header h is nonce start[h] + k mod 2^64.  A winner (difficulty
+// != 0 and result x difficulty < 2^256, pow_exceeds_target) lowers offset[h] to k: the smallest winning k
+// whatever the order the workgroups run in.  offset[h] is 0xFFFFFFFF before the launch and span <= 2^32 - 1.
+__global__ __launch_bounds__(FULL_THREADS) void k_ethash_search(Dataset ds, const uint32_t* __restrict__ hash32,
+                                                                const uint8_t* __restrict__ difficulty,
+                                                                const uint64_t* __restrict__ start, uint32_t span,
+                                                                uint32_t blocks_per_header,
+                                                                uint32_t* __restrict__ offset) {
+    __shared__ FullShared sh;
+    const uint32_t h = blockIdx.x / blocks_per_header;
+    const uint64_t k64 = (uint64_t)(blockIdx.x - h * blocks_per_header) * FULL_THREADS + threadIdx.x;
+    const bool live = k64 < span;
+    const uint32_t k = live ? (uint32_t)k64 : span - 1;
+    uint32_t hw[8];
+#pragma unroll
+    for (int w = 0; w < 8; w++) hw[w] = hash32[(size_t)h * 8 + w];
+    uint32_t digest[8], result[8];
+    hashimoto_full(digest, result, ds, hw, start[h] + k, sh);
+    uint32_t d[8];
+    load_row32(d, difficulty, h);
+    uint32_t dnz = 0;
+#pragma unroll
+    for (int w = 0; w < 8; w++) dnz |= d[w];
+    if (live && dnz != 0 && !pow_exceeds_target(result, d)) atomicMin(&offset[h], k);
+}
+
 static Cache make_cache_arg(const uint8_t* d_cache, uint64_t cache_bytes) {
     return Cache{(const uint4*)d_cache, mod_recip((uint32_t)(cache_bytes / HASH_BYTES))};
 }
@@ -150,6 +254,55 @@ hipError_t launch_ethash_verify(const uint8_t* d_cache, uint64_t cache_bytes, ui
                        make_cache_arg(d_cache, cache_bytes), mod_recip((uint32_t)(dataset_bytes / MIX_BYTES)),
                        (const uint32_t*)d_hash32, d_nonce, n, (uint8_t*)nullptr, (uint8_t*)nullptr, d_mix32,
                        d_difficulty32, d_status);
+    return hipGetLastError();
+}
+
+static Dataset make_dataset_arg(const uint8_t* d_dataset, uint64_t dataset_bytes) {
+    return Dataset{(const uint4*)d_dataset, mod_recip((uint32_t)(dataset_bytes / MIX_BYTES))};
+}
+
+static dim3 full_grid(uint32_t n) { return dim3((uint32_t)(((uint64_t)n + FULL_THREADS - 1) / FULL_THREADS)); }
+
+hipError_t launch_ethash_full(const uint8_t* d_dataset, uint64_t dataset_bytes, const uint8_t* d_hash32,
+                              const uint64_t* d_nonce, uint32_t n, uint8_t* d_mix32, uint8_t* d_result32,
+                              hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_ethash_full<FM_FULL>, full_grid(n), dim3(FULL_THREADS), 0, st,
+                       make_dataset_arg(d_dataset, dataset_bytes), (const uint32_t*)d_hash32, d_nonce, n, d_mix32,
+                       d_result32, (const uint8_t*)nullptr, (const uint8_t*)nullptr, (uint8_t*)nullptr,
+                       (const uint32_t*)nullptr, (uint64_t*)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_ethash_verify_full(const uint8_t* d_dataset, uint64_t dataset_bytes, const uint8_t* d_hash32,
+                                     const uint64_t* d_nonce, const uint8_t* d_mix32, const uint8_t* d_difficulty32,
+                                     uint32_t n, uint8_t* d_status, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_ethash_full<FM_VERIFY>, full_grid(n), dim3(FULL_THREADS), 0, st,
+                       make_dataset_arg(d_dataset, dataset_bytes), (const uint32_t*)d_hash32, d_nonce, n,
+                       (uint8_t*)nullptr, (uint8_t*)nullptr, d_mix32, d_difficulty32, d_status,
+                       (const uint32_t*)nullptr, (uint64_t*)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_ethash_search(const uint8_t* d_dataset, uint64_t dataset_bytes, const uint8_t* d_hash32,
+                                const uint8_t* d_difficulty32, const uint64_t* d_start, uint32_t n, uint32_t span,
+                                uint32_t* d_offset, hipStream_t st) {
+    if (n == 0 || span == 0) return hipSuccess;
+    const uint32_t bph = (uint32_t)(((uint64_t)span + FULL_THREADS - 1) / FULL_THREADS);
+    hipLaunchKernelGGL(k_ethash_search, dim3(n * bph), dim3(FULL_THREADS), 0, st,
+                       make_dataset_arg(d_dataset, dataset_bytes), (const uint32_t*)d_hash32, d_difficulty32, d_start,
+                       span, bph, d_offset);
+    return hipGetLastError();
+}
+
+hipError_t launch_ethash_finish(const uint8_t* d_dataset, uint64_t dataset_bytes, const uint8_t* d_hash32,
+                                const uint64_t* d_start, const uint32_t* d_offset, uint32_t n, uint64_t* d_nonce_out,
+                                uint8_t* d_mix32, uint8_t* d_result32, uint8_t* d_found, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_ethash_full<FM_FINISH>, full_grid(n), dim3(FULL_THREADS), 0, st,
+                       make_dataset_arg(d_dataset, dataset_bytes), (const uint32_t*)d_hash32, d_start, n, d_mix32,
+                       d_result32, (const uint8_t*)nullptr, (const uint8_t*)nullptr, d_found, d_offset, d_nonce_out);
     return hipGetLastError();
 }
 

@@ -173,5 +173,101 @@ GSV_DI bool pow_exceeds_target(const uint32_t (&result)[8], const uint32_t (&dif
     return (high | (uint32_t)carry | (uint32_t)(carry >> 32)) != 0;
 }
 
+// ---- hashimoto over the resident dataset (algorithm.go:393-405), shared by k_ethash_full, k_ethash_search and
+// the sealer's finish launch.  Keccak is one nonce per lane; the access loop is EIGHT adjacent lanes per nonce:
+// lane l of a group holds mix words 4l .. 4l + 3 and reads quarter l of the 128-byte page, so the group reads
+// one whole line per access and a wave instruction eight of them.  A group walks its eight nonces FULL_NI at a
+// time (independent chains, FULL_NI pages in flight per group).  Seeds go to the group and digest words come
+// back through LDS (96 bytes a lane); every lane of the workgroup must call this (two __syncthreads()).
+constexpr int FULL_THREADS = 256;
+constexpr int FULL_NI = 4;  // nonces a group interleaves; divides 8
+
+struct Dataset {
+    const uint4* pages;  // 128-byte aligned: a page is one cache line, eight uint4
+    ModRecip rr;         // of the page count, dataset_bytes / 128 (at most 2^31)
+};
+
+struct FullShared {
+    uint4 seed[FULL_THREADS * 4];
+    uint32_t digest[FULL_THREADS * 8];
+};
+
+template <int K>
+GSV_DI uint32_t comp(const uint4& v) {
+    if constexpr (K == 0) return v.x;
+    else if constexpr (K == 1) return v.y;
+    else if constexpr (K == 2) return v.z;
+    else return v.w;
+}
+
+// accesses i0 + K .. i0 + 31 of FULL_NI nonces, K a compile-time index: mix[(i0 + K) % 32] is component K % 4
+// of lane K / 4's register
+template <int K>
+GSV_DI void full_accesses(uint4 (&mix)[FULL_NI], const uint32_t (&head)[FULL_NI], const Dataset& ds, uint32_t i0,
+                          uint32_t l, int group_lane) {
+    if constexpr (K < 32) {
+        uint4 page[FULL_NI];
+        const uint4* at[FULL_NI];
+#pragma unroll
+        for (int c = 0; c < FULL_NI; c++) {
+            const uint32_t word = (uint32_t)__shfl((int)comp<K % 4>(mix[c]), group_lane + K / 4);
+            const uint32_t parent = mod_reduce(fnv((i0 + K) ^ head[c], word), ds.rr);
+            at[c] = ds.pages + ((size_t)parent * 8 + l);
+        }
+        // The FULL_NI loads issue back to back, and nothing crosses the two fences: left to itself the
+        // scheduler sinks each load to its own fnv, runs one chain ahead of the others and waits for every
+        // load alone (s_waitcnt vmcnt(0) after each: one line in flight per group)
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int c = 0; c < FULL_NI; c++) page[c] = *at[c];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int c = 0; c < FULL_NI; c++) {
+            mix[c].x = fnv(mix[c].x, page[c].x);
+            mix[c].y = fnv(mix[c].y, page[c].y);
+            mix[c].z = fnv(mix[c].z, page[c].z);
+            mix[c].w = fnv(mix[c].w, page[c].w);
+        }
+        full_accesses<K + 1>(mix, head, ds, i0, l, group_lane);
+    }
+}
+
+GSV_DI void hashimoto_full(uint32_t (&digest)[8], uint32_t (&result)[8], const Dataset& ds, const uint32_t (&hw)[8],
+                           uint64_t nonce, FullShared& sh) {
+    const uint32_t tid = threadIdx.x, l = tid & 7u, group = tid & ~7u;
+    const int group_lane = (int)((tid & 63u) & ~7u);
+    uint32_t seed[16];
+    keccak512_40(seed, hw, nonce);
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+        sh.seed[tid * 4 + q] = make_uint4(seed[4 * q], seed[4 * q + 1], seed[4 * q + 2], seed[4 * q + 3]);
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t s0 = 0; s0 < 8; s0 += FULL_NI) {
+        uint4 mix[FULL_NI];
+        uint32_t head[FULL_NI];
+#pragma unroll
+        for (int c = 0; c < FULL_NI; c++) {
+            const uint32_t src = (group + s0 + c) * 4;
+            mix[c] = sh.seed[src + (l & 3u)];  // mix = seed || seed: words 4l .. 4l + 3 are the seed's 4 (l % 4) ..
+            head[c] = sh.seed[src].x;
+        }
+#pragma unroll 1
+        for (uint32_t i0 = 0; i0 < 64; i0 += 32) full_accesses<0>(mix, head, ds, i0, l, group_lane);
+#pragma unroll
+        for (int c = 0; c < FULL_NI; c++)
+            sh.digest[(group + s0 + c) * 8 + l] = fnv(fnv(fnv(mix[c].x, mix[c].y), mix[c].z), mix[c].w);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const uint4 v = sh.seed[tid * 4 + q];
+        seed[4 * q] = v.x, seed[4 * q + 1] = v.y, seed[4 * q + 2] = v.z, seed[4 * q + 3] = v.w;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) digest[k] = sh.digest[tid * 8 + k];
+    keccak256_96(result, seed, digest);
+}
+
 }  // namespace ethash
 }  // namespace gsv

@@ -140,5 +140,26 @@ inline bool make_cache(const uint8_t seed[32], uint64_t bytes, uint8_t* out) {
     return true;
 }
 
+// ---- the sealer's rounds (gsv_ethash_seal_batch).  A search launch cannot be interrupted, so a round is
+// sized to SEAL_ROUND_ITEMS nonces, milliseconds of the full kernel, not to the caller's max_attempts:
+// `headers` headers (a slice of those still searching) try `span` nonces each.  span is a multiple of the
+// 256-lane workgroup unless the attempts left are fewer, never 0 while attempts are left, and headers * span
+// <= SEAL_ROUND_ITEMS.
+constexpr uint64_t SEAL_ROUND_ITEMS = 1ull << 22;
+constexpr uint64_t SEAL_BLOCK = 256;
+
+struct SealRound {
+    uint64_t headers, span;
+};
+
+inline SealRound seal_round(uint64_t searching, uint64_t attempts_left) {
+    if (searching == 0 || attempts_left == 0) return SealRound{0, 0};
+    const uint64_t max_headers = SEAL_ROUND_ITEMS / SEAL_BLOCK;
+    const uint64_t headers = searching < max_headers ? searching : max_headers;
+    uint64_t span = SEAL_ROUND_ITEMS / headers / SEAL_BLOCK * SEAL_BLOCK;  // >= SEAL_BLOCK: headers <= max_headers
+    if (span > attempts_left) span = attempts_left;
+    return SealRound{headers, span};
+}
+
 }  // namespace ethash
 }  // namespace gsv

@@ -4,7 +4,7 @@
 //   gsv_ecies.hip    ecies.Encrypt / Decrypt: the launch chains around the ladder
 //   gsv_txsign.hip   types.SignTx: the launch chain around the signature kernel
 //   gsv_modexp.hip   the modexp precompile: host grouping by modulus width, one launch per class
-//   gsv_ethash.hip   ethash: dataset items, hashimotoLight, VerifySeal; the host forms' epoch caches
+//   gsv_ethash.hip   ethash: dataset items, hashimotoLight / Full, VerifySeal, Seal; the epochs' caches and datasets
 //   gsv_trie.hip     chunk root, DeriveSha, Proof of Custody, collation headers
 //   gsv_pairing.hip  BN254 pairing check
 //   gsv_notary.hip   notary validation, shard partition + RCCL all-gather
@@ -190,8 +190,8 @@ struct gsv_ctx {
     struct Pending { int kid; hipEvent_t a, b; };
     std::vector<Pending> pending;
     std::vector<hipEvent_t> free_events;
-    double total_ms[GSV_K_TOP] = {0};
-    long launches[GSV_K_TOP] = {0};
+    double total_ms[GSV_K_PEAK] = {0};
+    long launches[GSV_K_PEAK] = {0};
     std::mutex tmu;
     std::vector<hipEvent_t> open_ev;  // timer events opened by launch hooks
     hipStream_t cur_stream = nullptr;  // stream of the shape run in progress (launch hooks)
@@ -230,6 +230,9 @@ struct gsv_ctx {
         uint64_t bytes;
     };
     std::list<EthashCache> ethash_caches;
+    // the epochs' datasets, generated on the device for the full and seal host forms: the same record, at
+    // most GSV_ETHASH_MAX_DATASETS, the same rule for freeing one
+    std::list<EthashCache> ethash_datasets;
 };
 
 namespace gsv {

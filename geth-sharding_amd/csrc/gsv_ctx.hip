@@ -319,6 +319,7 @@ void gsv_ctx_destroy(gsv_ctx* c) {
     if (c->hjoin) hipEventDestroy(c->hjoin);
     if (c->hside) hipStreamDestroy(c->hside);
     for (auto& e : c->ethash_caches) hipFree(e.d);
+    for (auto& e : c->ethash_datasets) hipFree(e.d);
     if (c->arena) hipFree(c->arena);
     if (c->gtab) hipFree(c->gtab);
     hipStreamDestroy(c->stream);
@@ -381,7 +382,7 @@ int gsv_ctx_set_pipeline_depth(gsv_ctx* c, int depth) {
 }
 
 int gsv_ctx_kernel_time(gsv_ctx* c, int kid, double* total_ms, long* launches) {
-    if (!c || kid < 0 || kid >= GSV_K_TOP) return GSV_E_INVALID_ARG;
+    if (!c || kid < 0 || kid >= GSV_K_PEAK) return GSV_E_INVALID_ARG;
     drain_timing(c);
     if (total_ms) *total_ms = c->total_ms[kid];
     if (launches) *launches = c->launches[kid];
@@ -391,7 +392,7 @@ int gsv_ctx_kernel_time(gsv_ctx* c, int kid, double* total_ms, long* launches) {
 int gsv_ctx_reset_timing(gsv_ctx* c) {
     if (!c) return GSV_E_INVALID_ARG;
     drain_timing(c);
-    for (int i = 0; i < GSV_K_TOP; i++) {
+    for (int i = 0; i < GSV_K_PEAK; i++) {
         c->total_ms[i] = 0;
         c->launches[i] = 0;
     }

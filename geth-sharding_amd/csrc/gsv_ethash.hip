@@ -1,6 +1,8 @@
-// ethash of the C ABI (gsv_ctx.h): the device forms check their arguments and enqueue one launch of
-// ethash.hip; the host forms group a batch by epoch, keep the epochs' verification caches on the device
-// (made on the host by ethash_host.h, outside the context's lock) and run one launch per epoch.
+// ethash of the C ABI (gsv_ctx.h): the device forms check their arguments and enqueue launches of ethash.hip
+// (one each; the search three nodes); the host forms group a batch by epoch, keep the epochs' verification
+// caches on the device (made on the host by ethash_host.h, outside the context's lock) and, for the full and
+// seal forms, the epochs' datasets (made on the device from those caches), and run one launch per epoch, the
+// sealer one search per round.
 #include <map>
 
 #include "ethash_host.h"
@@ -21,6 +23,10 @@ bool cache_ok(const uint8_t* d_cache, uint64_t cache_bytes) {
 
 bool dataset_ok(uint64_t dataset_bytes) {
     return dataset_bytes >= eth::MIX_BYTES && dataset_bytes % eth::MIX_BYTES == 0 && dataset_bytes <= MAX_DATASET;
+}
+
+bool full_dataset_ok(const uint8_t* d_dataset, uint64_t dataset_bytes) {
+    return d_dataset && ((uintptr_t)d_dataset & 127) == 0 && dataset_ok(dataset_bytes);
 }
 
 bool seed_ok(const uint8_t* d_hash32, const uint64_t* d_nonce) {
@@ -82,20 +88,77 @@ int epoch_cache(gsv_ctx* c, std::unique_lock<std::mutex>& lk, uint64_t epoch, bo
     return GSV_SUCCESS;
 }
 
-// light: a / b are the outputs (mix digest, result); verify: the inputs (mix digest, difficulty)
+// The device dataset of (epoch, test), called with the context's lock held and nothing of this context's
+// running (every host form synchronises before it releases the lock).  On a miss: the epoch's cache (which
+// may drop and retake the lock), then the new dataset's memory BEFORE anything is evicted, so a failed
+// allocation leaves the list as it was; then the least recently used go, and k_ethash_items fills the new one
+// on the context stream, which is waited for.
+int epoch_dataset(gsv_ctx* c, std::unique_lock<std::mutex>& lk, uint64_t epoch, bool test, const EpochSizes& sz,
+                  const uint8_t** d_dataset) {
+    auto find = [&]() {
+        for (auto it = c->ethash_datasets.begin(); it != c->ethash_datasets.end(); ++it)
+            if (it->epoch == epoch && it->test == test) {
+                c->ethash_datasets.splice(c->ethash_datasets.begin(), c->ethash_datasets, it);
+                return true;
+            }
+        return false;
+    };
+    if (!find()) {
+        const uint8_t* d_cache = nullptr;
+        int rc = epoch_cache(c, lk, epoch, test, sz, &d_cache);
+        if (rc) return rc;
+        if (!find()) {  // the lock may have been dropped for the cache: another call may have made it
+            HIPCHK(hipSetDevice(c->device));
+            uint8_t* d = nullptr;
+            if (hipMalloc(&d, sz.dataset_bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                return GSV_E_NOMEM;
+            }
+            const uint64_t items = sz.dataset_bytes / eth::HASH_BYTES;
+            for (uint64_t first = 0; first < items && rc == GSV_SUCCESS;) {
+                const uint64_t count = std::min<uint64_t>(items - first, 1ull << 31);
+                rc = gsv_ethash_dataset_items_dev(c, d_cache, sz.cache_bytes, first, count, d + first * eth::HASH_BYTES,
+                                                  c->stream);
+                first += count;
+            }
+            if (rc == GSV_SUCCESS && hipStreamSynchronize(c->stream) != hipSuccess) rc = GSV_E_HIP;
+            if (rc) {
+                hipFree(d);
+                return rc;
+            }
+            while (c->ethash_datasets.size() >= GSV_ETHASH_MAX_DATASETS) {
+                hipFree(c->ethash_datasets.back().d);
+                c->ethash_datasets.pop_back();
+            }
+            c->ethash_datasets.push_front({epoch, test, d, sz.dataset_bytes});
+        }
+    }
+    *d_dataset = c->ethash_datasets.front().d;
+    return GSV_SUCCESS;
+}
+
+// groups item indices by epoch; GSV_E_TOO_LARGE for an epoch whose dataset passes MAX_DATASET
+int group_by_epoch(const uint64_t* number, size_t n, bool test, std::map<uint64_t, std::vector<uint32_t>>& groups) {
+    for (size_t i = 0; i < n; i++) {
+        const uint64_t epoch = number[i] / eth::EPOCH_LENGTH;
+        if (!test && epoch >= MAX_EPOCH) return GSV_E_TOO_LARGE;
+        groups[epoch].push_back((uint32_t)i);
+    }
+    return GSV_SUCCESS;
+}
+
+// light / full: a / b are the outputs (mix digest, result); verify: the inputs (mix digest, difficulty).  full
+// reads the epoch's dataset instead of its cache.
 int host_batch(gsv_ctx* c, const uint64_t* number, bool test, const uint8_t* hash32, const uint64_t* nonce, size_t n,
-               bool verify, const uint8_t* a_in, const uint8_t* b_in, uint8_t* a_out, uint8_t* b_out,
+               bool verify, bool full, const uint8_t* a_in, const uint8_t* b_in, uint8_t* a_out, uint8_t* b_out,
                uint8_t* status) {
     if (!c || n > MAX_N) return GSV_E_INVALID_ARG;
     if (n == 0) return GSV_SUCCESS;
     if (!number || !hash32 || !nonce) return GSV_E_INVALID_ARG;
     if (verify ? (!a_in || !b_in || !status) : (!a_out || !b_out)) return GSV_E_INVALID_ARG;
     std::map<uint64_t, std::vector<uint32_t>> groups;
-    for (size_t i = 0; i < n; i++) {
-        const uint64_t epoch = number[i] / eth::EPOCH_LENGTH;
-        if (!test && epoch >= MAX_EPOCH) return GSV_E_TOO_LARGE;
-        groups[epoch].push_back((uint32_t)i);
-    }
+    int grc = group_by_epoch(number, n, test, groups);
+    if (grc) return grc;
     std::vector<uint8_t> h, a, b, st;
     std::vector<uint64_t> nn;
     std::unique_lock<std::mutex> lk(c->mu);
@@ -103,8 +166,9 @@ int host_batch(gsv_ctx* c, const uint64_t* number, bool test, const uint8_t* has
         const std::vector<uint32_t>& items = g.second;
         const size_t m = items.size();
         const EpochSizes sz = epoch_sizes(g.first, test);
-        const uint8_t* d_cache = nullptr;
-        int rc = epoch_cache(c, lk, g.first, test, sz, &d_cache);
+        const uint8_t *d_cache = nullptr, *d_dataset = nullptr;
+        int rc = full ? epoch_dataset(c, lk, g.first, test, sz, &d_dataset)
+                      : epoch_cache(c, lk, g.first, test, sz, &d_cache);
         if (rc) return rc;
         HIPCHK(hipSetDevice(c->device));
         h.resize(m * 32);
@@ -137,8 +201,9 @@ int host_batch(gsv_ctx* c, const uint64_t* number, bool test, const uint8_t* has
             if (rc) return rc;
             HIPCHK(hipMemcpyAsync(st.data(), d_st, m, hipMemcpyDeviceToHost, c->stream));
         } else {
-            rc = gsv_ethash_light_batch_dev(c, d_cache, sz.cache_bytes, sz.dataset_bytes, d_h, d_n, m, d_a, d_b,
-                                            c->stream);
+            rc = full ? gsv_ethash_full_batch_dev(c, d_dataset, sz.dataset_bytes, d_h, d_n, m, d_a, d_b, c->stream)
+                      : gsv_ethash_light_batch_dev(c, d_cache, sz.cache_bytes, sz.dataset_bytes, d_h, d_n, m, d_a, d_b,
+                                                   c->stream);
             if (rc) return rc;
             HIPCHK(hipMemcpyAsync(a.data(), d_a, m * 32, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipMemcpyAsync(b.data(), d_b, m * 32, hipMemcpyDeviceToHost, c->stream));
@@ -198,15 +263,167 @@ int gsv_ethash_verify_seal_batch_dev(gsv_ctx* c, const uint8_t* d_cache, uint64_
 
 int gsv_ethash_light_batch(gsv_ctx* c, const uint64_t* number, int test_mode, const uint8_t* hash32,
                            const uint64_t* nonce, size_t n, uint8_t* mix32_out, uint8_t* result32_out) {
-    return host_batch(c, number, test_mode != 0, hash32, nonce, n, false, nullptr, nullptr, mix32_out, result32_out,
-                      nullptr);
+    return host_batch(c, number, test_mode != 0, hash32, nonce, n, false, false, nullptr, nullptr, mix32_out,
+                      result32_out, nullptr);
 }
 
 int gsv_ethash_verify_seal_batch(gsv_ctx* c, const uint64_t* number, const uint8_t* hash32, const uint64_t* nonce,
                                  const uint8_t* mix32, const uint8_t* difficulty32, size_t n, int test_mode,
                                  uint8_t* status) {
-    return host_batch(c, number, test_mode != 0, hash32, nonce, n, true, mix32, difficulty32, nullptr, nullptr,
+    return host_batch(c, number, test_mode != 0, hash32, nonce, n, true, false, mix32, difficulty32, nullptr, nullptr,
                       status);
+}
+
+int gsv_ethash_full_batch_dev(gsv_ctx* c, const uint8_t* d_dataset, uint64_t dataset_bytes, const uint8_t* d_hash32,
+                              const uint64_t* d_nonce, size_t n, uint8_t* d_mix32, uint8_t* d_result32, void* stream) {
+    if (!c || !full_dataset_ok(d_dataset, dataset_bytes) || n > MAX_N) return GSV_E_INVALID_ARG;
+    if (n == 0) return GSV_SUCCESS;
+    if (!seed_ok(d_hash32, d_nonce) || !d_mix32 || !d_result32) return GSV_E_INVALID_ARG;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    KTimer t(c, GSV_K_ETHASH_FULL, st);
+    return hip_err(gsv::launch_ethash_full(d_dataset, dataset_bytes, d_hash32, d_nonce, (uint32_t)n, d_mix32,
+                                           d_result32, st));
+}
+
+int gsv_ethash_verify_seal_full_batch_dev(gsv_ctx* c, const uint8_t* d_dataset, uint64_t dataset_bytes,
+                                          const uint8_t* d_hash32, const uint64_t* d_nonce, const uint8_t* d_mix32,
+                                          const uint8_t* d_difficulty32, size_t n, uint8_t* d_status, void* stream) {
+    if (!c || !full_dataset_ok(d_dataset, dataset_bytes) || n > MAX_N) return GSV_E_INVALID_ARG;
+    if (n == 0) return GSV_SUCCESS;
+    if (!seed_ok(d_hash32, d_nonce) || !d_mix32 || !d_difficulty32 || !d_status) return GSV_E_INVALID_ARG;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    KTimer t(c, GSV_K_ETHASH_FULL, st);
+    return hip_err(gsv::launch_ethash_verify_full(d_dataset, dataset_bytes, d_hash32, d_nonce, d_mix32,
+                                                  d_difficulty32, (uint32_t)n, d_status, st));
+}
+
+int gsv_ethash_search_dev(gsv_ctx* c, const uint8_t* d_dataset, uint64_t dataset_bytes, const uint8_t* d_hash32,
+                          const uint8_t* d_difficulty32, const uint64_t* d_start, size_t n, uint64_t span,
+                          uint32_t* d_offset, uint64_t* d_nonce_out, uint8_t* d_mix32, uint8_t* d_result32,
+                          uint8_t* d_found, void* stream) {
+    if (!c || !full_dataset_ok(d_dataset, dataset_bytes) || n > MAX_N) return GSV_E_INVALID_ARG;
+    if (n == 0) return GSV_SUCCESS;
+    if (span == 0 || span > 0xFFFFFFFFull || (uint64_t)n * ((span + 255) / 256) > MAX_N) return GSV_E_INVALID_ARG;
+    if (!seed_ok(d_hash32, d_start) || !d_difficulty32 || !d_offset || ((uintptr_t)d_offset & 3) || !d_nonce_out ||
+        ((uintptr_t)d_nonce_out & 7) || !d_mix32 || !d_result32 || !d_found)
+        return GSV_E_INVALID_ARG;
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    // A 32-bit fill, not hipMemsetAsync(.., 0xFF, 4 n).  An observation, seen in one test run and not traced
+    // to its cause: with the byte form captured into a graph and d_offset at 4 mod 16, the three words in front
+    // of the first 16-byte boundary read zero after the replay, so those headers "won" at offset 0; the same
+    // call outside a capture filled them.  tests/test_gpu_ethash_full.py test_dev_form_contract keeps d_offset
+    // at 4 mod 16 and passes with this form.
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)d_offset, (int)0xFFFFFFFFu, n, st));
+    {
+        KTimer t(c, GSV_K_ETHASH_SEARCH, st);
+        int rc = hip_err(gsv::launch_ethash_search(d_dataset, dataset_bytes, d_hash32, d_difficulty32, d_start,
+                                                   (uint32_t)n, (uint32_t)span, d_offset, st));
+        if (rc) return rc;
+    }
+    KTimer t(c, GSV_K_ETHASH_FINISH, st);
+    return hip_err(gsv::launch_ethash_finish(d_dataset, dataset_bytes, d_hash32, d_start, d_offset, (uint32_t)n,
+                                             d_nonce_out, d_mix32, d_result32, d_found, st));
+}
+
+int gsv_ethash_full_batch(gsv_ctx* c, const uint64_t* number, int test_mode, const uint8_t* hash32,
+                          const uint64_t* nonce, size_t n, uint8_t* mix32_out, uint8_t* result32_out) {
+    return host_batch(c, number, test_mode != 0, hash32, nonce, n, false, true, nullptr, nullptr, mix32_out,
+                      result32_out, nullptr);
+}
+
+int gsv_ethash_seal_batch(gsv_ctx* c, const uint64_t* number, int test_mode, const uint8_t* hash32,
+                          const uint8_t* difficulty32, const uint64_t* start_nonce, size_t n, uint64_t max_attempts,
+                          uint64_t* nonce_out, uint8_t* mix32_out, uint8_t* status) {
+    if (!c || n > MAX_N) return GSV_E_INVALID_ARG;
+    if (n == 0) return GSV_SUCCESS;
+    if (!number || !hash32 || !difficulty32 || !start_nonce || !nonce_out || !mix32_out || !status)
+        return GSV_E_INVALID_ARG;
+    const bool test = test_mode != 0;
+    std::map<uint64_t, std::vector<uint32_t>> groups;
+    int rc = group_by_epoch(number, n, test, groups);
+    if (rc) return rc;
+    memset(nonce_out, 0, n * sizeof(uint64_t));
+    memset(mix32_out, 0, n * 32);
+    static const uint8_t zero32[32] = {0};
+    std::vector<uint8_t> h, d, mix, found;
+    std::vector<uint64_t> start, won;
+    std::unique_lock<std::mutex> lk(c->mu);
+    for (const auto& g : groups) {
+        // the headers still searching, with the nonce each tries next; all have been tried `tried` times
+        std::vector<uint32_t> items;
+        std::vector<uint64_t> next;
+        for (uint32_t i : g.second) {
+            if (memcmp(difficulty32 + (size_t)i * 32, zero32, 32) == 0) {
+                status[i] = GSV_ST_INVALID_DIFFICULTY;
+                continue;
+            }
+            status[i] = GSV_ST_NONCE_NOT_FOUND;
+            items.push_back(i);
+            next.push_back(start_nonce[i]);
+        }
+        if (items.empty() || max_attempts == 0) continue;
+        const EpochSizes sz = epoch_sizes(g.first, test);
+        const uint8_t* d_dataset = nullptr;
+        rc = epoch_dataset(c, lk, g.first, test, sz, &d_dataset);
+        if (rc) return rc;
+        HIPCHK(hipSetDevice(c->device));
+        for (uint64_t tried = 0; tried < max_attempts && !items.empty();) {
+            const eth::SealRound round = eth::seal_round(items.size(), max_attempts - tried);
+            std::vector<uint32_t> keep_items;
+            std::vector<uint64_t> keep_next;
+            for (size_t at = 0; at < items.size(); at += round.headers) {
+                const size_t m = std::min<size_t>(round.headers, items.size() - at);
+                h.resize(m * 32);
+                d.resize(m * 32);
+                mix.resize(m * 32);
+                found.resize(m);
+                start.resize(m);
+                won.resize(m);
+                for (size_t k = 0; k < m; k++) {
+                    memcpy(&h[k * 32], hash32 + (size_t)items[at + k] * 32, 32);
+                    memcpy(&d[k * 32], difficulty32 + (size_t)items[at + k] * 32, 32);
+                    start[k] = next[at + k];
+                }
+                Layout L;
+                const EthashSealStage p(L, m);
+                rc = arena_reserve(c, L.n);
+                if (rc) return rc;
+                HIPCHK(hipMemcpyAsync(p.hash(c->arena), h.data(), m * 32, hipMemcpyHostToDevice, c->stream));
+                HIPCHK(hipMemcpyAsync(p.diff(c->arena), d.data(), m * 32, hipMemcpyHostToDevice, c->stream));
+                HIPCHK(hipMemcpyAsync(p.start(c->arena), start.data(), m * 8, hipMemcpyHostToDevice, c->stream));
+                rc = gsv_ethash_search_dev(c, d_dataset, sz.dataset_bytes, p.hash(c->arena), p.diff(c->arena),
+                                           p.start(c->arena), m, round.span, p.offset(c->arena), p.nonce(c->arena),
+                                           p.mix(c->arena), p.result(c->arena), p.found(c->arena), c->stream);
+                if (rc) return rc;
+                HIPCHK(hipMemcpyAsync(won.data(), p.nonce(c->arena), m * 8, hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(hipMemcpyAsync(mix.data(), p.mix(c->arena), m * 32, hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(hipMemcpyAsync(found.data(), p.found(c->arena), m, hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(hipStreamSynchronize(c->stream));
+                for (size_t k = 0; k < m; k++) {
+                    const uint32_t i = items[at + k];
+                    if (found[k]) {
+                        status[i] = GSV_ST_OK;
+                        nonce_out[i] = won[k];
+                        memcpy(mix32_out + (size_t)i * 32, &mix[k * 32], 32);
+                    } else {
+                        keep_items.push_back(i);
+                        keep_next.push_back(next[at + k] + round.span);  // mod 2^64
+                    }
+                }
+            }
+            items.swap(keep_items);
+            next.swap(keep_next);
+            tried += round.span;
+        }
+    }
+    return GSV_SUCCESS;
+}
+
+int gsv_ctx_ethash_datasets(gsv_ctx* c, size_t* count) {
+    if (!c || !count) return GSV_E_INVALID_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    *count = c->ethash_datasets.size();
+    return GSV_SUCCESS;
 }
 
 int gsv_ctx_ethash_caches(gsv_ctx* c, size_t* count) {

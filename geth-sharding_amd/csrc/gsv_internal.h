@@ -161,6 +161,21 @@ hipError_t launch_ethash_light(const uint8_t* d_cache, uint64_t cache_bytes, uin
 hipError_t launch_ethash_verify(const uint8_t* d_cache, uint64_t cache_bytes, uint64_t dataset_bytes,
                                 const uint8_t* d_hash32, const uint64_t* d_nonce, const uint8_t* d_mix32,
                                 const uint8_t* d_difficulty32, uint32_t n, uint8_t* d_status, hipStream_t st);
+// the same over the dataset itself (128-byte aligned, dataset_bytes of it); search: n headers x span nonces
+// from d_start[h], n * ceil(span / 256) workgroups, d_offset[h] pre-set to 0xFFFFFFFF; finish: the rows of
+// nonce d_start[h] + d_offset[h] where an offset was left, zeros and d_found[h] = 0 elsewhere
+hipError_t launch_ethash_full(const uint8_t* d_dataset, uint64_t dataset_bytes, const uint8_t* d_hash32,
+                              const uint64_t* d_nonce, uint32_t n, uint8_t* d_mix32, uint8_t* d_result32,
+                              hipStream_t st);
+hipError_t launch_ethash_verify_full(const uint8_t* d_dataset, uint64_t dataset_bytes, const uint8_t* d_hash32,
+                                     const uint64_t* d_nonce, const uint8_t* d_mix32, const uint8_t* d_difficulty32,
+                                     uint32_t n, uint8_t* d_status, hipStream_t st);
+hipError_t launch_ethash_search(const uint8_t* d_dataset, uint64_t dataset_bytes, const uint8_t* d_hash32,
+                                const uint8_t* d_difficulty32, const uint64_t* d_start, uint32_t n, uint32_t span,
+                                uint32_t* d_offset, hipStream_t st);
+hipError_t launch_ethash_finish(const uint8_t* d_dataset, uint64_t dataset_bytes, const uint8_t* d_hash32,
+                                const uint64_t* d_start, const uint32_t* d_offset, uint32_t n, uint64_t* d_nonce_out,
+                                uint8_t* d_mix32, uint8_t* d_result32, uint8_t* d_found, hipStream_t st);
 
 // collation.hip: CollationHeader.Hash() with ProposerSignature empty (k_header_hash alone: the hash the
 // proposer signs), no nil fields

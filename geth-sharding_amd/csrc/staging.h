@@ -260,6 +260,16 @@ struct EthashStage {
         : hash(L.buf(n * 32)), nonce(L.buf<uint64_t>(n * 8)), a(L.buf(n * 32)), b(L.buf(n * 32)),
           st(L.buf(n, verify)) {}
 };
+// gsv_ethash_seal_batch, one round's slice of headers: what gsv_ethash_search_dev reads and writes
+struct EthashSealStage {
+    B8 hash, diff;
+    Buf<uint64_t> start, nonce;
+    Buf<uint32_t> offset;
+    B8 mix, result, found;
+    EthashSealStage(Layout& L, size_t n)
+        : hash(L.buf(n * 32)), diff(L.buf(n * 32)), start(L.buf<uint64_t>(n * 8)), nonce(L.buf<uint64_t>(n * 8)),
+          offset(L.buf<uint32_t>(n * 4)), mix(L.buf(n * 32)), result(L.buf(n * 32)), found(L.buf(n)) {}
+};
 
 }  // namespace api
 }  // namespace gsv

@@ -1157,6 +1157,83 @@ def _ethash_caches(self) -> int:
     return cnt.value
 
 
+def _ethash_dataset_bytes(dataset_t) -> int:
+    if not dataset_t.is_contiguous():
+        raise ValueError("ethash: the dataset is a contiguous tensor of its bytes")
+    return dataset_t.numel() * dataset_t.element_size()
+
+
+def _ethash_full_batch_dev(self, dataset_t, hash_t, nonce_t, mix_t, result_t, stream=None, n=None):
+    """hashimotoFull over torch CUDA tensors: dataset_t the dataset's bytes (128-byte aligned; its size is the
+    tensor's), the rest as ethash_light_batch_dev.  Only enqueues on `stream`: one launch."""
+    n = int(nonce_t.numel()) if n is None else int(n)
+    check(_lib.load().gsv_ethash_full_batch_dev(self._h, _tptr(dataset_t), _ethash_dataset_bytes(dataset_t),
+                                                _tptr(hash_t), _tptr(nonce_t), n, _tptr(mix_t), _tptr(result_t),
+                                                _sp(stream)))
+
+
+def _ethash_verify_seal_full_batch_dev(self, dataset_t, hash_t, nonce_t, mix_t, difficulty_t, status_t, stream=None,
+                                       n=None):
+    """As ethash_verify_seal_batch_dev, over the dataset."""
+    n = int(nonce_t.numel()) if n is None else int(n)
+    check(_lib.load().gsv_ethash_verify_seal_full_batch_dev(self._h, _tptr(dataset_t),
+                                                            _ethash_dataset_bytes(dataset_t), _tptr(hash_t),
+                                                            _tptr(nonce_t), _tptr(mix_t), _tptr(difficulty_t), n,
+                                                            _tptr(status_t), _sp(stream)))
+
+
+def _ethash_search_dev(self, dataset_t, hash_t, difficulty_t, start_t, span: int, offset_t, nonce_out_t, mix_t,
+                       result_t, found_t, stream=None, n=None):
+    """The nonce search over torch CUDA tensors (gsv.h gsv_ethash_search_dev): header h tries start_t[h] + k for
+    k < span; offset_t (n int32 / uint32) gets the smallest winning k or 0xFFFFFFFF, nonce_out_t (n int64 /
+    uint64), mix_t / result_t (n rows of 32 bytes) and found_t (n bytes) the winner's.  Only enqueues on
+    `stream`: a memset, the search launch and the finish launch."""
+    n = int(start_t.numel()) if n is None else int(n)
+    check(_lib.load().gsv_ethash_search_dev(self._h, _tptr(dataset_t), _ethash_dataset_bytes(dataset_t),
+                                            _tptr(hash_t), _tptr(difficulty_t), _tptr(start_t), n, int(span),
+                                            _tptr(offset_t), _tptr(nonce_out_t), _tptr(mix_t), _tptr(result_t),
+                                            _tptr(found_t), _sp(stream)))
+
+
+def _ethash_full_batch(self, numbers, hashes, nonces, test_mode=False):
+    """hashimotoFull per (block number, hash without nonce, nonce) (gsv.h gsv_ethash_full_batch): as
+    ethash_light_batch, over the epochs' datasets, which the context generates on the device and keeps."""
+    h, nn = _ethash_rows(hashes, nonces)
+    num = np.ascontiguousarray(numbers, np.uint64).reshape(-1)
+    n = h.shape[0]
+    if num.shape[0] != n:
+        raise ValueError("ethash: one block number per item")
+    mix = np.zeros((n, 32), np.uint8)
+    res = np.zeros((n, 32), np.uint8)
+    check(_lib.load().gsv_ethash_full_batch(self._h, _ptr(num), int(bool(test_mode)), _ptr(h), _ptr(nn), n, _ptr(mix),
+                                            _ptr(res)))
+    return mix, res
+
+
+def _ethash_seal_batch(self, numbers, hashes, difficulties, start_nonces, max_attempts: int, test_mode=False):
+    """The sealer per header (gsv.h gsv_ethash_seal_batch): difficulties (n, 32) big-endian.  Returns (nonces
+    (n,) uint64, mix digests (n, 32), status (n,) uint8: ST_OK, ST_INVALID_DIFFICULTY or ST_NONCE_NOT_FOUND)."""
+    h, st0 = _ethash_rows(hashes, start_nonces)
+    num = np.ascontiguousarray(numbers, np.uint64).reshape(-1)
+    dif = _rows32(difficulties)
+    n = h.shape[0]
+    if num.shape[0] != n or dif.shape[0] != n:
+        raise ValueError("ethash: one block number and difficulty per item")
+    nonce = np.zeros(n, np.uint64)
+    mix = np.zeros((n, 32), np.uint8)
+    st = np.zeros(n, np.uint8)
+    check(_lib.load().gsv_ethash_seal_batch(self._h, _ptr(num), int(bool(test_mode)), _ptr(h), _ptr(dif), _ptr(st0), n,
+                                            int(max_attempts), _ptr(nonce), _ptr(mix), _ptr(st)))
+    return nonce, mix, st
+
+
+def _ethash_datasets(self) -> int:
+    """epoch datasets the context holds for the ethash full and seal forms (at most _lib.ETHASH_MAX_DATASETS)"""
+    cnt = ctypes.c_size_t()
+    check(_lib.load().gsv_ctx_ethash_datasets(self._h, ctypes.byref(cnt)))
+    return cnt.value
+
+
 def _arena_read(self, off, n):
     """Test hook (gsv.h gsv_ctx_arena_read): n bytes of the staging arena from `off`, as they are now."""
     out = np.zeros(n, np.uint8)
@@ -1197,6 +1274,12 @@ Context.ethash_dataset_items_dev = _ethash_dataset_items_dev
 Context.ethash_light_batch_dev = _ethash_light_batch_dev
 Context.ethash_verify_seal_batch_dev = _ethash_verify_seal_batch_dev
 Context.ethash_caches = _ethash_caches
+Context.ethash_full_batch = _ethash_full_batch
+Context.ethash_seal_batch = _ethash_seal_batch
+Context.ethash_full_batch_dev = _ethash_full_batch_dev
+Context.ethash_verify_seal_full_batch_dev = _ethash_verify_seal_full_batch_dev
+Context.ethash_search_dev = _ethash_search_dev
+Context.ethash_datasets = _ethash_datasets
 Context.modexp_batch = _modexp_batch
 Context.modexp_batch_dev = _modexp_batch_dev
 Context._arena_read = _arena_read

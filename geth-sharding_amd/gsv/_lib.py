@@ -33,6 +33,7 @@ ST_MODEXP_TOO_LONG = 15
 ST_INVALID_DIFFICULTY = 16
 ST_INVALID_MIX_DIGEST = 17
 ST_INVALID_POW = 18
+ST_NONCE_NOT_FOUND = 19
 
 # a short text per per-item status: the reference's error string where it has one (include/gsv.h names
 # the sources)
@@ -56,6 +57,7 @@ STATUS_STRINGS = {
     ST_INVALID_DIFFICULTY: "non-positive difficulty",
     ST_INVALID_MIX_DIGEST: "invalid mix digest",
     ST_INVALID_POW: "invalid proof-of-work",
+    ST_NONCE_NOT_FOUND: "ethash: no nonce found within max_attempts",
 }
 
 SIGNER_EIP155 = 0
@@ -86,9 +88,14 @@ K_SHA256 = 16
 K_RIPEMD160 = 17
 K_ETHASH_ITEMS = 18
 K_ETHASH_LIGHT = 19
-K_TOP = 20  # GSV_K_TOP: gsv_ctx_kernel_time takes every id below it
+K_TOP = 20  # GSV_K_TOP: pinned; the ids behind it follow
+K_ETHASH_FULL = 20
+K_ETHASH_SEARCH = 21
+K_ETHASH_FINISH = 22
+K_PEAK = 23  # GSV_K_PEAK: gsv_ctx_kernel_time takes every id below it
 
 ETHASH_MAX_CACHES = 3  # GSV_ETHASH_MAX_CACHES: epoch caches a context keeps for the ethash host forms
+ETHASH_MAX_DATASETS = 2  # GSV_ETHASH_MAX_DATASETS: epoch datasets a context keeps for the full and seal forms
 
 MODEXP_MAX_LEN = 1024  # GSV_MODEXP_MAX_LEN: the cap on baseLen, expLen and modLen of the modexp precompile
 
@@ -206,6 +213,12 @@ SIGNATURES = [
     ("gsv_ethash_light_batch", ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, _sz, _vp, _vp]),
     ("gsv_ethash_verify_seal_batch", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_int, _vp]),
     ("gsv_ctx_ethash_caches", ctypes.c_int, [_vp, ctypes.POINTER(_sz)]),
+    ("gsv_ethash_full_batch_dev", ctypes.c_int, [_vp, _vp, _u64, _vp, _vp, _sz, _vp, _vp, _vp]),
+    ("gsv_ethash_verify_seal_full_batch_dev", ctypes.c_int, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    ("gsv_ethash_search_dev", ctypes.c_int, [_vp, _vp, _u64, _vp, _vp, _vp, _sz, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("gsv_ethash_full_batch", ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, _sz, _vp, _vp]),
+    ("gsv_ethash_seal_batch", ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, _vp, _sz, _u64, _vp, _vp, _vp]),
+    ("gsv_ctx_ethash_datasets", ctypes.c_int, [_vp, ctypes.POINTER(_sz)]),
     ("gsv_chunk_root_prepare", ctypes.c_int, [_vp, _vp, _sz]),
     ("gsv_bn256_pairing_prepare", ctypes.c_int, [_vp, _vp, _sz]),
     ("gsv_notary_prepare", ctypes.c_int, [_vp, _vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_uint32]),

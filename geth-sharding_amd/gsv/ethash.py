@@ -1,16 +1,22 @@
-"""Mirror of the reference's consensus/ethash, the part a light verifier runs, batched on the GPU.
+"""Mirror of the reference's consensus/ethash: the seal check of a light verifier and the sealer's search,
+batched on the GPU.
 
     cacheSize(block), datasetSize(block)   algorithm.go:53-91 (the formula; the tables hold its values)
     seedHash(block)                        algorithm.go:110-120
     generateCache(size, seed)              algorithm.go:128-197, on the host (include/gsv.h says why)
     generateDatasetItems(cache, first, count)   generateDatasetItem over a range: the body of generateDataset
+    generateDataset(size, cache)                algorithm.go:265-328 -> the dataset as a device tensor
     hashimotoLight(size, cache, hash, nonce)    algorithm.go:375 -> (digest, result)
     hashimotoLightBatch(size, cache, hashes, nonces)
+    hashimotoFull(dataset, hash, nonce)         algorithm.go:393-405 -> (digest, result)
+    hashimotoFullBatch(dataset, hashes, nonces)
     Ethash(test_mode).VerifySeal / VerifySeals  consensus.go:463-501, by block number
+    Ethash(test_mode).hashimotoFull             by block number, over the context's epoch datasets
+    Ethash(test_mode).Seal / SealBatch          the search of mine (sealer.go:97-152), by block number
 
 The nonce is the number (Header.Nonce.Uint64()); types.BlockNonce is its big-endian bytes.  Not here:
-Header.HashNoNonce() from the header's RLP (Context.keccak256_batch makes it), the rest of verifyHeader,
-hashimotoFull, the sealer and cache files on disk.
+Header.HashNoNonce() from the header's RLP (Context.keccak256_batch makes it), the rest of verifyHeader, DAG
+and cache files on disk, remote mining / GetWork, and pre-generating the next epoch.
 """
 from __future__ import annotations
 
@@ -107,6 +113,50 @@ def hashimotoLight(size: int, cache, hash: bytes, nonce: int, ctx=None):
     return mix[0].tobytes(), res[0].tobytes()
 
 
+def generateDataset(size: int, cache, ctx=None):
+    """the dataset of `size` bytes (a multiple of 128) over `cache`, generated on the device: a CUDA uint8
+    tensor of `size` bytes, which hashimotoFull and Context.ethash_search_dev read in place"""
+    import torch
+    size = int(size)
+    if size < 128 or size % 128:
+        raise ValueError("ethash: the dataset size is a multiple of 128 bytes")
+    ctx = ctx or default_context()
+    d_cache = _device_cache(cache, ctx)
+    out = torch.empty(size, dtype=torch.uint8, device=d_cache.device)
+    items, step = size // 64, 1 << 31
+    for first in range(0, items, step):
+        count = min(step, items - first)
+        ctx.ethash_dataset_items_dev(d_cache, first, count, out[first * 64:(first + count) * 64])
+    torch.cuda.synchronize(d_cache.device)
+    return out
+
+
+def hashimotoFullBatch(dataset, hashes, nonces, ctx=None):
+    """(digests (n, 32), results (n, 32)) of hashimotoFull(dataset, hashes[i], nonces[i]); dataset is
+    generateDataset's tensor (or the dataset's bytes on the host, uploaded here)"""
+    import torch
+    ctx = ctx or default_context()
+    d_set = _device_cache(dataset, ctx)
+    h = _rows32(hashes)
+    nn = np.ascontiguousarray(nonces, np.uint64).reshape(-1)
+    n = h.shape[0]
+    if nn.shape[0] != n:
+        raise ValueError("ethash: one 32-byte hash and one nonce per item")
+    dev = d_set.device
+    d_h = torch.from_numpy(h).to(dev)
+    d_n = torch.from_numpy(nn.view(np.int64)).to(dev)
+    d_mix = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+    d_res = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+    ctx.ethash_full_batch_dev(d_set, d_h, d_n, d_mix, d_res, n=n)
+    torch.cuda.synchronize(dev)
+    return d_mix.cpu().numpy(), d_res.cpu().numpy()
+
+
+def hashimotoFull(dataset, hash: bytes, nonce: int, ctx=None):
+    mix, res = hashimotoFullBatch(dataset, [bytes(hash)], [int(nonce)], ctx)
+    return mix[0].tobytes(), res[0].tobytes()
+
+
 def _difficulty_rows(difficulties) -> np.ndarray:
     """32 bytes big-endian per difficulty.  Negative means non-positive (row of zeros: ErrInvalidDifficulty);
     2^256 and more cannot be written in 32 bytes and is handled by the caller."""
@@ -152,6 +202,54 @@ class Ethash:
                 if res[k].any():
                     st[i] = _lib.ST_INVALID_POW
         return st
+
+    def hashimotoFull(self, numbers, hashes, nonces):
+        """as hashimotoLight, over the epochs' datasets (generated on the device, at most
+        _lib.ETHASH_MAX_DATASETS kept by the context)"""
+        return self.ctx.ethash_full_batch(numbers, hashes, nonces, self.test_mode)
+
+    def SealBatch(self, numbers, hashes_no_nonce, difficulties, start_nonces, max_attempts: int):
+        """The sealer's search per header: (nonces (n,) uint64, mix digests (n, 32), status (n,) uint8: ST_OK,
+        ST_INVALID_DIFFICULTY or ST_NONCE_NOT_FOUND).  Header i tries start_nonces[i], start_nonces[i] + 1, ...
+        (mod 2^64) for at most max_attempts nonces and reports the FIRST whose result is within the target:
+        what mine() finds from that seed as the only thread.  difficulties: Python ints, or (n, 32) big-endian
+        rows."""
+        max_attempts = int(max_attempts)
+        if isinstance(difficulties, np.ndarray) and difficulties.dtype == np.uint8:
+            return self.ctx.ethash_seal_batch(numbers, hashes_no_nonce, difficulties, start_nonces, max_attempts,
+                                              self.test_mode)
+        difficulties = [int(d) for d in difficulties]
+        # 2^256 and more: target 0, only a zero result seals.  As in VerifySeals the library sees 2^256 - 1
+        # (target 1); a winner whose result is one is passed over here and the search goes on behind it.
+        big = [i for i, d in enumerate(difficulties) if d > MAX_UINT256]
+        rows = _difficulty_rows([MAX_UINT256 if d > MAX_UINT256 else d for d in difficulties])
+        nonce, mix, st = self.ctx.ethash_seal_batch(numbers, hashes_no_nonce, rows, start_nonces, max_attempts,
+                                                    self.test_mode)
+        if big:
+            num = np.ascontiguousarray(numbers, np.uint64).reshape(-1)
+            h = _rows32(hashes_no_nonce)
+            first = np.ascontiguousarray(start_nonces, np.uint64).reshape(-1)
+            for i in big:
+                while st[i] == _lib.ST_OK:
+                    _, res = self.ctx.ethash_full_batch(num[i:i + 1], h[i:i + 1], nonce[i:i + 1], self.test_mode)
+                    if not res.any():
+                        break
+                    used = ((int(nonce[i]) - int(first[i])) % (1 << 64)) + 1
+                    nxt = np.array([(int(nonce[i]) + 1) % (1 << 64)], np.uint64)
+                    n1, m1, s1 = self.ctx.ethash_seal_batch(num[i:i + 1], h[i:i + 1], rows[i:i + 1], nxt,
+                                                            max_attempts - used, self.test_mode)
+                    nonce[i], mix[i], st[i] = n1[0], m1[0], s1[0]
+        return nonce, mix, st
+
+    def Seal(self, number: int, hash_no_nonce: bytes, difficulty: int, start_nonce: int, max_attempts: int):
+        """(nonce, mix digest) of the first seal at or after start_nonce, or None when none lies within
+        max_attempts nonces.  Raises ErrInvalidDifficulty for a non-positive difficulty."""
+        nonce, mix, st = self.SealBatch([number], [bytes(hash_no_nonce)], [difficulty], [start_nonce], max_attempts)
+        if st[0] == _lib.ST_INVALID_DIFFICULTY:
+            raise ErrInvalidDifficulty(_lib.STATUS_STRINGS[_lib.ST_INVALID_DIFFICULTY])
+        if st[0] != _lib.ST_OK:
+            return None
+        return int(nonce[0]), mix[0].tobytes()
 
     def VerifySeal(self, number: int, hash_no_nonce: bytes, nonce: int, mix_digest: bytes, difficulty: int) -> None:
         st = int(self.VerifySeals([number], [bytes(hash_no_nonce)], [nonce], [bytes(mix_digest)], [difficulty])[0])

@@ -132,6 +132,8 @@ extern "C" {
 #define GSV_ST_INVALID_DIFFICULTY 16 /* ethash errInvalidDifficulty    consensus/ethash/consensus.go:56 */
 #define GSV_ST_INVALID_MIX_DIGEST 17 /* ethash errInvalidMixDigest     consensus/ethash/consensus.go:57 */
 #define GSV_ST_INVALID_POW 18        /* ethash errInvalidPoW           consensus/ethash/consensus.go:58 */
+#define GSV_ST_NONCE_NOT_FOUND 19    /* the sealer gave up after max_attempts nonces: not the reference's, whose
+                                        mine() runs until it is aborted (consensus/ethash/sealer.go:110-118) */
 
 /* signer kinds for gsv_tx_sender_batch and gsv_tx_sign_batch (core/types/transaction_signing.go) */
 #define GSV_SIGNER_EIP155 0
@@ -194,6 +196,12 @@ int gsv_ctx_set_timing(gsv_ctx *ctx, int enable);
 #define GSV_K_ETHASH_ITEMS 18 /* ethash dataset items: one launch per call */
 #define GSV_K_ETHASH_LIGHT 19 /* ethash hashimotoLight / VerifySeal: one launch per call */
 #define GSV_K_TOP 20
+/* Ids added behind GSV_K_TOP (pinned like the five before it); gsv_ctx_kernel_time takes every id below
+ * GSV_K_PEAK. */
+#define GSV_K_ETHASH_FULL 20   /* ethash hashimotoFull / VerifySeal over the dataset: one launch per call */
+#define GSV_K_ETHASH_SEARCH 21 /* ethash nonce search: one launch per gsv_ethash_search_dev */
+#define GSV_K_ETHASH_FINISH 22 /* the search's finish launch (the winners' rows): one per gsv_ethash_search_dev */
+#define GSV_K_PEAK 23
 /* total milliseconds and launch count accumulated for kernel `kid` since the last reset */
 int gsv_ctx_kernel_time(gsv_ctx *ctx, int kid, double *total_ms, long *launches);
 int gsv_ctx_reset_timing(gsv_ctx *ctx);
@@ -626,12 +634,13 @@ size_t gsv_modexp_work_bytes(size_t n, uint32_t base_len, uint32_t exp_len, uint
 int gsv_modexp_batch_dev(gsv_ctx *ctx, const uint8_t *d_in, size_t n, uint32_t base_len, uint32_t exp_len,
                          uint32_t mod_len, uint8_t *d_out, uint8_t *d_work, void *stream);
 
-/* ---- ethash (consensus/ethash): hashimotoLight, VerifySeal, dataset items ----
+/* ---- ethash (consensus/ethash): hashimotoLight, VerifySeal, dataset items, hashimotoFull, Seal ----
  * What Ethash.VerifyHeaders (consensus.go:90) spends its time in: VerifySeal (consensus.go:463-501) runs
  * hashimotoLight (algorithm.go:375) per header over the epoch's verification cache.  An epoch is 30,000
- * blocks.  Not here: Header.HashNoNonce() from the header's RLP (callers pass the 32-byte hash;
- * gsv_keccak256_batch makes it from the 13-field RLP), the rest of verifyHeader (timestamps, gas limits,
- * CalcDifficulty), hashimotoFull with full-DAG storage and the sealer, and cache files on disk.
+ * blocks.  The sealing half follows below the light forms.  Not here: Header.HashNoNonce() from the header's
+ * RLP (callers pass the 32-byte hash; gsv_keccak256_batch makes it from the 13-field RLP), the rest of
+ * verifyHeader (timestamps, gas limits, CalcDifficulty), DAG and cache files on disk, remote mining / GetWork,
+ * and pre-generating the next epoch.
  *
  * Host only, no context: cacheSize / datasetSize (algorithm.go:53-91) by the reference's formula for every
  * epoch (its 2,048-entry tables hold the same values), seedHash (algorithm.go:110-120) and generateCache
@@ -684,6 +693,62 @@ int gsv_ethash_verify_seal_batch(gsv_ctx *ctx, const uint64_t *number, const uin
                                  const uint8_t *mix32, const uint8_t *difficulty32, size_t n, int test_mode,
                                  uint8_t *status);
 int gsv_ctx_ethash_caches(gsv_ctx *ctx, size_t *count);
+/* The sealing half: hashimotoFull (algorithm.go:393-405) and the nonce search of mine (sealer.go:97-152) over
+ * the dataset itself, resident on the device: 2 permutations and 64 reads of one 128-byte page per nonce.
+ * A dataset in device form is gsv_ethash_dataset_items_dev over items [0, dataset_bytes / 64) (a 2^38-byte one
+ * takes two calls: first + count <= 2^32 and count < 2^32).
+ *
+ * Device-resident.  Each only enqueues on `stream` (NULL = the context stream): no allocation, no
+ * synchronisation, no prepare call, capturable; n == 0: success, nothing enqueued.  GSV_E_INVALID_ARG:
+ * dataset_bytes below 128, no multiple of 128 or above 2^38; d_dataset off 128-byte alignment (a page is one
+ * cache line); hash rows off 4-byte, nonces / starts / d_nonce_out off 8-byte, d_offset off 4-byte alignment;
+ * n above 2^31 - 1; span == 0 or above 2^32 - 1; n * ceil(span / 256) above 2^31 - 1 (the grid).  Rows of mix
+ * digests, results and difficulties may have any byte alignment.
+ *   full:    one launch (GSV_K_ETHASH_FULL): (d_mix32 row i, d_result32 row i) = hashimotoFull(dataset,
+ *            d_hash32 row i, d_nonce[i]), the nonce as a NUMBER as in the light form.
+ *   verify:  one launch (GSV_K_ETHASH_FULL): d_status[i] by the light form's three checks in its order.
+ *   search:  a fill of d_offset with 0xFFFFFFFF (a memset node), one search launch (GSV_K_ETHASH_SEARCH) and
+ *            one finish launch (GSV_K_ETHASH_FINISH).  Header h tries nonces d_start[h] + k mod 2^64 for
+ *            k < span, as the reference's nonce++ wraps.  A winner has result <= floor((2^256 - 1) /
+ *            difficulty), decided exactly by the 512-bit product as in verify; d_offset[h] is the SMALLEST
+ *            winning k whatever the order the hardware ran them in, or 0xFFFFFFFF.  Then d_found[h] = 1,
+ *            d_nonce_out[h] the winning nonce and (d_mix32, d_result32) row h its hashimotoFull; with no
+ *            winner d_found[h] = 0 and the three are zeros.  A header whose difficulty is zero never wins
+ *            (the reference would panic on the division).  Size span so that a launch is milliseconds:
+ *            the kernels cannot be interrupted. */
+int gsv_ethash_full_batch_dev(gsv_ctx *ctx, const uint8_t *d_dataset, uint64_t dataset_bytes,
+                              const uint8_t *d_hash32, const uint64_t *d_nonce, size_t n, uint8_t *d_mix32,
+                              uint8_t *d_result32, void *stream);
+int gsv_ethash_verify_seal_full_batch_dev(gsv_ctx *ctx, const uint8_t *d_dataset, uint64_t dataset_bytes,
+                                          const uint8_t *d_hash32, const uint64_t *d_nonce, const uint8_t *d_mix32,
+                                          const uint8_t *d_difficulty32, size_t n, uint8_t *d_status, void *stream);
+int gsv_ethash_search_dev(gsv_ctx *ctx, const uint8_t *d_dataset, uint64_t dataset_bytes, const uint8_t *d_hash32,
+                          const uint8_t *d_difficulty32, const uint64_t *d_start, size_t n, uint64_t span,
+                          uint32_t *d_offset, uint64_t *d_nonce_out, uint8_t *d_mix32, uint8_t *d_result32,
+                          uint8_t *d_found, void *stream);
+/* Host forms by block number, grouped by epoch like the light forms.  The epoch's dataset is generated on the
+ * device from the epoch's cached verification cache (1 GiB at epoch 0, growing 8 MiB an epoch; test_mode: 32
+ * KiB, ethash.go:294-299) and kept: a context holds at most GSV_ETHASH_MAX_DATASETS, least recently used out
+ * first, freed under the caches' rule (only inside a host call that holds the lock and has synchronised).  A
+ * failed allocation returns GSV_E_NOMEM and leaves the list as it was.  gsv_ctx_ethash_datasets: how many the
+ * context holds now.
+ *   full:  (mix32_out row i, result32_out row i) = hashimotoFull for number[i]'s epoch.
+ *   seal:  per header the search above from start_nonce[i], in rounds of a bounded span (a launch stays in
+ *          the milliseconds, so max_attempts is honoured to the round); a header leaves the later rounds once
+ *          found, and the call ends when every header is found or has been tried max_attempts times.
+ *          status[i] = GSV_ST_OK with nonce_out[i] and mix32_out row i; GSV_ST_INVALID_DIFFICULTY for a zero
+ *          difficulty; GSV_ST_NONCE_NOT_FOUND (zeros) otherwise.  nonce_out[i] is the FIRST winner at or after
+ *          start_nonce[i]: (nonce, mix digest) are what mine(block, id, seed = start_nonce[i], ...) reports
+ *          when it runs as the only thread, whenever that nonce lies within max_attempts of the seed.
+ *          Ethash.Seal with several threads returns whichever thread wins a race, each a valid seal; this is
+ *          the deterministic one. */
+#define GSV_ETHASH_MAX_DATASETS 2
+int gsv_ethash_full_batch(gsv_ctx *ctx, const uint64_t *number, int test_mode, const uint8_t *hash32,
+                          const uint64_t *nonce, size_t n, uint8_t *mix32_out, uint8_t *result32_out);
+int gsv_ethash_seal_batch(gsv_ctx *ctx, const uint64_t *number, int test_mode, const uint8_t *hash32,
+                          const uint8_t *difficulty32, const uint64_t *start_nonce, size_t n, uint64_t max_attempts,
+                          uint64_t *nonce_out, uint8_t *mix32_out, uint8_t *status);
+int gsv_ctx_ethash_datasets(gsv_ctx *ctx, size_t *count);
 
 /* ---- synthetic signed workload (bench / test data generator; signing is not on the path) ----
  * key_i, msg_i, nonce_i = Keccak256(le64(seed) || le64(i) || "key"/"msg"/"nce"), key and nonce
