@@ -17,9 +17,8 @@
 //   k_ethash_search  the same body over n headers x span nonces, the inner loop of mine (sealer.go:97-152): a
 //                    winner lowers its header's offset by atomicMin
 //
-// Out of scope here: Header.HashNoNonce() from the header's RLP (callers pass the 32-byte hash;
-// gsv_keccak256_batch makes it from the 13-field RLP), the rest of verifyHeader (timestamps, gas limits,
-// CalcDifficulty), DAG and cache files on disk, remote mining / GetWork, and pre-generating the next epoch.
+// The header's RLP, Header.HashNoNonce() and the rest of verifyHeader are block_header.hip.  Out of scope: DAG and
+// cache files on disk, remote mining / GetWork, and pre-generating the next epoch.
 #include "ethash_dev.cuh"
 #include "ethash_host.h"
 #include "gsv_internal.h"

@@ -5,6 +5,7 @@
 //   gsv_txsign.hip   types.SignTx: the launch chain around the signature kernel
 //   gsv_modexp.hip   the modexp precompile: host grouping by modulus width, one launch per class
 //   gsv_ethash.hip   ethash: dataset items, hashimotoLight / Full, VerifySeal, Seal; the epochs' caches and datasets
+//   gsv_block_header.hip  types.Header hashes, CalcDifficulty, Ethash.VerifyHeaders: the launch chain around the seal
 //   gsv_trie.hip     chunk root, DeriveSha, Proof of Custody, collation headers
 //   gsv_pairing.hip  BN254 pairing check
 //   gsv_notary.hip   notary validation, shard partition + RCCL all-gather
@@ -190,8 +191,8 @@ struct gsv_ctx {
     struct Pending { int kid; hipEvent_t a, b; };
     std::vector<Pending> pending;
     std::vector<hipEvent_t> free_events;
-    double total_ms[GSV_K_PEAK] = {0};
-    long launches[GSV_K_PEAK] = {0};
+    double total_ms[GSV_K_SUMMIT] = {0};
+    long launches[GSV_K_SUMMIT] = {0};
     std::mutex tmu;
     std::vector<hipEvent_t> open_ev;  // timer events opened by launch hooks
     hipStream_t cur_stream = nullptr;  // stream of the shape run in progress (launch hooks)
@@ -293,6 +294,12 @@ int chunk_run(gsv_ctx* c, const Shape& s, const ChunkLaunch& cl, const uint8_t* 
 uint64_t stage_offsets(const uint64_t* off, size_t n, std::vector<uint64_t>& st, std::vector<uint64_t>& en);
 int stage_bodies(gsv_ctx* c, uint8_t* d_b, const uint8_t* bodies, const uint64_t* off, size_t n,
                  const std::vector<uint64_t>& st, const std::vector<uint64_t>& en);
+// ---- gsv_ethash.hip: VerifySeal's checks over host arrays grouped by epoch (gsv_ethash_verify_seal_batch), for a
+// caller that holds the context's lock `lk` (it may be dropped and retaken while a cache is generated).  Uses the
+// arena and synchronises.
+int ethash_verify_seal_host(gsv_ctx* c, std::unique_lock<std::mutex>& lk, const uint64_t* number, bool test,
+                            const uint8_t* hash32, const uint64_t* nonce, const uint8_t* mix32,
+                            const uint8_t* difficulty32, size_t n, uint8_t* status);
 // ---- gsv_pairing.hip
 int bn_depth_class(int depth);
 // ---- gsv_notary.hip

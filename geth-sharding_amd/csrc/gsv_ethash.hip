@@ -149,9 +149,10 @@ int group_by_epoch(const uint64_t* number, size_t n, bool test, std::map<uint64_
 
 // light / full: a / b are the outputs (mix digest, result); verify: the inputs (mix digest, difficulty).  full
 // reads the epoch's dataset instead of its cache.
-int host_batch(gsv_ctx* c, const uint64_t* number, bool test, const uint8_t* hash32, const uint64_t* nonce, size_t n,
-               bool verify, bool full, const uint8_t* a_in, const uint8_t* b_in, uint8_t* a_out, uint8_t* b_out,
-               uint8_t* status) {
+// With the context's lock held in `lk`.
+int host_batch_locked(gsv_ctx* c, std::unique_lock<std::mutex>& lk, const uint64_t* number, bool test,
+                      const uint8_t* hash32, const uint64_t* nonce, size_t n, bool verify, bool full,
+                      const uint8_t* a_in, const uint8_t* b_in, uint8_t* a_out, uint8_t* b_out, uint8_t* status) {
     if (!c || n > MAX_N) return GSV_E_INVALID_ARG;
     if (n == 0) return GSV_SUCCESS;
     if (!number || !hash32 || !nonce) return GSV_E_INVALID_ARG;
@@ -161,7 +162,6 @@ int host_batch(gsv_ctx* c, const uint64_t* number, bool test, const uint8_t* has
     if (grc) return grc;
     std::vector<uint8_t> h, a, b, st;
     std::vector<uint64_t> nn;
-    std::unique_lock<std::mutex> lk(c->mu);
     for (const auto& g : groups) {
         const std::vector<uint32_t>& items = g.second;
         const size_t m = items.size();
@@ -222,7 +222,28 @@ int host_batch(gsv_ctx* c, const uint64_t* number, bool test, const uint8_t* has
     return GSV_SUCCESS;
 }
 
+int host_batch(gsv_ctx* c, const uint64_t* number, bool test, const uint8_t* hash32, const uint64_t* nonce, size_t n,
+               bool verify, bool full, const uint8_t* a_in, const uint8_t* b_in, uint8_t* a_out, uint8_t* b_out,
+               uint8_t* status) {
+    if (!c) return GSV_E_INVALID_ARG;
+    std::unique_lock<std::mutex> lk(c->mu);
+    return host_batch_locked(c, lk, number, test, hash32, nonce, n, verify, full, a_in, b_in, a_out, b_out, status);
+}
+
 }  // namespace
+
+namespace gsv {
+namespace api {
+
+int ethash_verify_seal_host(gsv_ctx* c, std::unique_lock<std::mutex>& lk, const uint64_t* number, bool test,
+                            const uint8_t* hash32, const uint64_t* nonce, const uint8_t* mix32,
+                            const uint8_t* difficulty32, size_t n, uint8_t* status) {
+    return host_batch_locked(c, lk, number, test, hash32, nonce, n, true, false, mix32, difficulty32, nullptr, nullptr,
+                             status);
+}
+
+}  // namespace api
+}  // namespace gsv
 
 extern "C" {
 

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/gsv.h"
+#include "block_header_host.h"
 
 namespace gsv {
 
@@ -176,6 +177,21 @@ hipError_t launch_ethash_search(const uint8_t* d_dataset, uint64_t dataset_bytes
 hipError_t launch_ethash_finish(const uint8_t* d_dataset, uint64_t dataset_bytes, const uint8_t* d_hash32,
                                 const uint64_t* d_start, const uint32_t* d_offset, uint32_t n, uint64_t* d_nonce_out,
                                 uint8_t* d_mix32, uint8_t* d_result32, uint8_t* d_found, hipStream_t st);
+
+// block_header.hip: types.Header decode + Hash / HashNoNonce into the records of d_work (bh::work_bytes(n) bytes, 16-byte
+// aligned; entry n is the parent of header 0, parent_len == 0: none), the rules of verifyHeader around the seal, the
+// merge of the three statuses, and CalcDifficulty alone over n decoded parents.  Output rows that are null are not
+// written; d_hnn32 is 4-byte and d_nonce / d_number / d_time 8-byte aligned
+hipError_t launch_block_header(const uint8_t* d_rlp, const uint64_t* d_off, uint32_t n, const uint8_t* d_parent_rlp,
+                               uint32_t parent_len, uint8_t* d_work, uint8_t* d_hash32, uint8_t* d_hnn32,
+                               uint64_t* d_nonce, uint8_t* d_mix32, uint8_t* d_difficulty32, uint64_t* d_number,
+                               uint8_t* d_status, hipStream_t st);
+hipError_t launch_block_header_rules(uint8_t* d_work, uint32_t n, const bh::Config& cfg, uint64_t now, uint8_t* d_pre,
+                                     uint8_t* d_post, uint8_t* d_want32, hipStream_t st);
+hipError_t launch_block_header_merge(const uint8_t* d_pre, const uint8_t* d_seal, const uint8_t* d_seals,
+                                     const uint8_t* d_post, uint32_t n, uint8_t* d_status, hipStream_t st);
+hipError_t launch_calc_difficulty(uint8_t* d_work, uint32_t n, const bh::Config& cfg, const uint64_t* d_time,
+                                  uint8_t* d_want32, uint8_t* d_status, hipStream_t st);
 
 // collation.hip: CollationHeader.Hash() with ProposerSignature empty (k_header_hash alone: the hash the
 // proposer signs), no nil fields

@@ -254,6 +254,30 @@ GSV_DI void keccak256_xy(uint32_t h[8], const uint32_t x[8], const uint32_t y[8]
     }
 }
 
+// One rate block (17 little-endian 64-bit words) of the message at p, `avail` bytes of it valid
+// (>= 136: a full block).  Messages sit at any byte offset (RLP strings packed back to back), so the
+// block is read as up to 35 aligned dwords from p rounded down to 4 and realigned with
+// v_alignbyte_b32 — 35 loads instead of 136 byte loads.  A dword is read only if it holds a valid
+// byte (so never past the page of the last one); bytes past `avail` are masked to zero.
+GSV_DI void load_block(uint64_t w[17], const uint8_t* p, uint32_t avail) {
+    const uint32_t* q = (const uint32_t*)((uintptr_t)p & ~(uintptr_t)3);
+    uint32_t sh = (uint32_t)((uintptr_t)p & 3u);
+    uint32_t take = avail < 136u ? avail : 136u;
+    uint32_t need = sh + take;  // bytes from q
+    uint32_t d[35];
+#pragma unroll
+    for (int j = 0; j < 35; j++) d[j] = (4u * j < need) ? q[j] : 0u;
+#pragma unroll
+    for (int k = 0; k < 17; k++) {
+        uint32_t lo = __builtin_amdgcn_alignbyte(d[2 * k + 1], d[2 * k], sh);
+        uint32_t hi = __builtin_amdgcn_alignbyte(d[2 * k + 2], d[2 * k + 1], sh);
+        uint64_t v = (uint64_t)lo | ((uint64_t)hi << 32);
+        int32_t valid = (int32_t)take - 8 * k;
+        if (valid < 8) v = valid <= 0 ? 0 : v & ((1ull << (8 * valid)) - 1);
+        w[k] = v;
+    }
+}
+
 // Lane-to-item order for a 256-thread workgroup whose lanes each absorb a variable number of rate
 // blocks: a wave runs as many permutations as its longest message, so with tx-sized messages (one or
 // two blocks) half a wave would idle through the second one.  Every thread passes its item's block

@@ -270,6 +270,23 @@ struct EthashSealStage {
         : hash(L.buf(n * 32)), diff(L.buf(n * 32)), start(L.buf<uint64_t>(n * 8)), nonce(L.buf<uint64_t>(n * 8)),
           offset(L.buf<uint32_t>(n * 4)), mix(L.buf(n * 32)), result(L.buf(n * 32)), found(L.buf(n)) {}
 };
+// gsv_block_header_hash_batch, gsv_calc_difficulty_batch, gsv_ethash_verify_headers_batch: the items (and the
+// parent of header 0), the records (`work`, bh::work_bytes(n)) and what the launches write.  `time` is the
+// difficulty form's input; hnn .. diff are the arrays the seal call takes; pre is the decode status of the
+// hash and difficulty forms.
+struct BlockHeaderStage {
+    B8 rlp;
+    Buf<uint64_t> off;
+    B8 parent, work, hash, hnn;
+    Buf<uint64_t> nonce, number, time;
+    B8 mix, diff, want, pre, post;
+    BlockHeaderStage(Layout& L, size_t bytes, size_t n, size_t parent_len, size_t work_bytes, bool rules, bool calc)
+        : rlp(L.buf(bytes + 8)), off(L.buf<uint64_t>((n + 1) * 8)), parent(L.buf(parent_len + 8, parent_len != 0)),
+          work(L.buf(work_bytes)), hash(L.buf(n * 32, !calc)), hnn(L.buf(n * 32, !calc)),
+          nonce(L.buf<uint64_t>(n * 8, rules)), number(L.buf<uint64_t>(n * 8, rules)),
+          time(L.buf<uint64_t>(n * 8, calc)), mix(L.buf(n * 32, rules)), diff(L.buf(n * 32, rules)),
+          want(L.buf(n * 32, rules || calc)), pre(L.buf(n)), post(L.buf(n, rules)) {}
+};
 
 }  // namespace api
 }  // namespace gsv

@@ -1234,6 +1234,89 @@ def _ethash_datasets(self) -> int:
     return cnt.value
 
 
+def _config_ref(config):
+    """a gsv.params.ChainConfig (or a _lib.ChainConfigStruct) as the pointer the C ABI takes"""
+    st = config if isinstance(config, _lib.ChainConfigStruct) else config.as_struct()
+    return st, ctypes.cast(ctypes.pointer(st), ctypes.c_void_p)
+
+
+def _block_header_hash_batch(self, headers):
+    """Header.Hash() and Header.HashNoNonce() of RLP-encoded headers (gsv.h gsv_block_header_hash_batch).  Returns
+    (hashes (n, 32), hashes without nonce (n, 32), status (n,): ST_OK, ST_BAD_RLP or ST_HEADER_TOO_WIDE)."""
+    headers = [bytes(h) for h in headers]
+    n = len(headers)
+    flat, off = _pack(headers)
+    h = np.zeros((n, 32), np.uint8)
+    hnn = np.zeros((n, 32), np.uint8)
+    st = np.zeros(n, np.uint8)
+    check(_lib.load().gsv_block_header_hash_batch(self._h, _ptr(flat), _ptr(off), n, _ptr(h), _ptr(hnn), _ptr(st)))
+    return h, hnn, st
+
+
+def _calc_difficulty_batch(self, config, times, parents):
+    """CalcDifficulty(config, times[i], parents[i]) over RLP-encoded parents (gsv.h gsv_calc_difficulty_batch).
+    Returns (difficulties (n, 32) big-endian, status (n,))."""
+    parents = [bytes(h) for h in parents]
+    n = len(parents)
+    t = np.ascontiguousarray(times, np.uint64).reshape(-1)
+    if t.shape[0] != n:
+        raise ValueError("headers: one time per parent")
+    flat, off = _pack(parents)
+    out = np.zeros((n, 32), np.uint8)
+    st = np.zeros(n, np.uint8)
+    keep, cfg = _config_ref(config)
+    check(_lib.load().gsv_calc_difficulty_batch(self._h, cfg, _ptr(t), _ptr(flat), _ptr(off), n, _ptr(out), _ptr(st)))
+    return out, st
+
+
+def _ethash_verify_headers_batch(self, config, headers, seals=None, parent=None, now=0, test_mode=False,
+                                 want_hash=False, want_expected=False):
+    """Ethash.VerifyHeaders over RLP-encoded headers (gsv.h gsv_ethash_verify_headers_batch): status (n,) uint8, or
+    (status, hashes or None, expected difficulties or None) when one of the two is asked for."""
+    headers = [bytes(h) for h in headers]
+    n = len(headers)
+    flat, off = _pack(headers)
+    par = _np_u8(parent) if parent else None
+    sl = None
+    if seals is not None:
+        sl = np.ascontiguousarray(np.asarray(seals, bool).astype(np.uint8)).reshape(-1)
+        if sl.shape[0] != n:
+            raise ValueError("headers: one seal flag per header")
+    st = np.zeros(n, np.uint8)
+    h = np.zeros((n, 32), np.uint8) if want_hash else None
+    want = np.zeros((n, 32), np.uint8) if want_expected else None
+    keep, cfg = _config_ref(config)
+    check(_lib.load().gsv_ethash_verify_headers_batch(self._h, cfg, _ptr(flat), _ptr(off), n, _ptr(par),
+                                                      0 if par is None else par.size, _ptr(sl), int(now),
+                                                      int(bool(test_mode)), _ptr(st), _ptr(h), _ptr(want)))
+    return (st, h, want) if (want_hash or want_expected) else st
+
+
+def block_header_work_bytes(n: int) -> int:
+    """gsv_block_header_work_bytes: the work area of block_header_rules_dev"""
+    return int(_lib.load().gsv_block_header_work_bytes(int(n)))
+
+
+def _block_header_rules_dev(self, config, rlp_t, off_t, n: int, parent_t, now: int, work_t, hnn_t, nonce_t, mix_t,
+                            difficulty_t, pre_t, post_t, hash_t=None, number_t=None, expected_t=None, stream=None):
+    """Decode + rules over torch CUDA tensors (gsv.h gsv_block_header_rules_dev): rlp_t the headers' bytes, off_t
+    n + 1 int64 offsets, parent_t the parent's RLP or None.  Writes what ethash_verify_seal_batch_dev takes (hnn_t,
+    nonce_t, mix_t, difficulty_t) and the pre- and post-seal statuses.  Only enqueues on `stream`: two launches."""
+    keep, cfg = _config_ref(config)
+    plen = 0 if parent_t is None else int(parent_t.numel())
+    check(_lib.load().gsv_block_header_rules_dev(self._h, cfg, _tptr(rlp_t), _tptr(off_t), int(n), _tptr(parent_t),
+                                                 plen, int(now), _tptr(work_t), _tptr(hnn_t), _tptr(nonce_t),
+                                                 _tptr(mix_t), _tptr(difficulty_t), _tptr(pre_t), _tptr(post_t),
+                                                 _tptr(hash_t), _tptr(number_t), _tptr(expected_t), _sp(stream)))
+
+
+def _block_header_merge_dev(self, pre_t, seal_t, seals_t, post_t, status_t, n=None, stream=None):
+    """status = pre, else the seal's where asked for, else post (gsv.h gsv_block_header_merge_dev): one launch"""
+    n = int(pre_t.numel()) if n is None else int(n)
+    check(_lib.load().gsv_block_header_merge_dev(self._h, _tptr(pre_t), _tptr(seal_t), _tptr(seals_t), _tptr(post_t),
+                                                 n, _tptr(status_t), _sp(stream)))
+
+
 def _arena_read(self, off, n):
     """Test hook (gsv.h gsv_ctx_arena_read): n bytes of the staging arena from `off`, as they are now."""
     out = np.zeros(n, np.uint8)
@@ -1280,6 +1363,11 @@ Context.ethash_full_batch_dev = _ethash_full_batch_dev
 Context.ethash_verify_seal_full_batch_dev = _ethash_verify_seal_full_batch_dev
 Context.ethash_search_dev = _ethash_search_dev
 Context.ethash_datasets = _ethash_datasets
+Context.block_header_hash_batch = _block_header_hash_batch
+Context.calc_difficulty_batch = _calc_difficulty_batch
+Context.ethash_verify_headers_batch = _ethash_verify_headers_batch
+Context.block_header_rules_dev = _block_header_rules_dev
+Context.block_header_merge_dev = _block_header_merge_dev
 Context.modexp_batch = _modexp_batch
 Context.modexp_batch_dev = _modexp_batch_dev
 Context._arena_read = _arena_read

@@ -34,6 +34,19 @@ ST_INVALID_DIFFICULTY = 16
 ST_INVALID_MIX_DIGEST = 17
 ST_INVALID_POW = 18
 ST_NONCE_NOT_FOUND = 19
+ST_HEADER_TOO_WIDE = 20
+ST_UNKNOWN_ANCESTOR = 21
+ST_EXTRA_TOO_LONG = 22
+ST_FUTURE_BLOCK = 23
+ST_ZERO_BLOCK_TIME = 24
+ST_WRONG_DIFFICULTY = 25
+ST_GAS_LIMIT_CAP = 26
+ST_GAS_USED = 27
+ST_GAS_LIMIT_BOUNDS = 28
+ST_INVALID_NUMBER = 29
+ST_BAD_PRO_DAO_EXTRA = 30
+ST_BAD_NO_DAO_EXTRA = 31
+ST_FORK_HASH = 32
 
 # a short text per per-item status: the reference's error string where it has one (include/gsv.h names
 # the sources)
@@ -58,6 +71,19 @@ STATUS_STRINGS = {
     ST_INVALID_MIX_DIGEST: "invalid mix digest",
     ST_INVALID_POW: "invalid proof-of-work",
     ST_NONCE_NOT_FOUND: "ethash: no nonce found within max_attempts",
+    ST_HEADER_TOO_WIDE: "header: Difficulty or Time above 32 bytes, or Number above 8",
+    ST_UNKNOWN_ANCESTOR: "unknown ancestor",
+    ST_EXTRA_TOO_LONG: "extra-data too long",
+    ST_FUTURE_BLOCK: "block in the future",
+    ST_ZERO_BLOCK_TIME: "timestamp equals parent's",
+    ST_WRONG_DIFFICULTY: "invalid difficulty",
+    ST_GAS_LIMIT_CAP: "invalid gasLimit",
+    ST_GAS_USED: "invalid gasUsed",
+    ST_GAS_LIMIT_BOUNDS: "invalid gas limit",
+    ST_INVALID_NUMBER: "invalid block number",
+    ST_BAD_PRO_DAO_EXTRA: "bad DAO pro-fork extra-data",
+    ST_BAD_NO_DAO_EXTRA: "bad DAO no-fork extra-data",
+    ST_FORK_HASH: "homestead gas reprice fork: wrong hash",
 }
 
 SIGNER_EIP155 = 0
@@ -92,7 +118,11 @@ K_TOP = 20  # GSV_K_TOP: pinned; the ids behind it follow
 K_ETHASH_FULL = 20
 K_ETHASH_SEARCH = 21
 K_ETHASH_FINISH = 22
-K_PEAK = 23  # GSV_K_PEAK: gsv_ctx_kernel_time takes every id below it
+K_PEAK = 23  # GSV_K_PEAK: pinned; the ids behind it follow
+K_BLOCK_HEADER = 23
+K_BLOCK_RULES = 24
+K_BLOCK_MERGE = 25
+K_SUMMIT = 26  # GSV_K_SUMMIT: gsv_ctx_kernel_time takes every id below it
 
 ETHASH_MAX_CACHES = 3  # GSV_ETHASH_MAX_CACHES: epoch caches a context keeps for the ethash host forms
 ETHASH_MAX_DATASETS = 2  # GSV_ETHASH_MAX_DATASETS: epoch datasets a context keeps for the full and seal forms
@@ -123,6 +153,16 @@ _u64p = ctypes.POINTER(ctypes.c_uint64)
 _vp = ctypes.c_void_p
 _sz = ctypes.c_size_t
 _u64 = ctypes.c_uint64
+
+
+class ChainConfigStruct(ctypes.Structure):
+    """gsv_chain_config (include/gsv.h): the fields of params.ChainConfig the header rules read"""
+    _fields_ = [("homestead_block", ctypes.c_uint64), ("dao_fork_block", ctypes.c_uint64),
+                ("eip150_block", ctypes.c_uint64), ("byzantium_block", ctypes.c_uint64),
+                ("has_homestead", ctypes.c_uint8), ("has_dao_fork", ctypes.c_uint8), ("has_eip150", ctypes.c_uint8),
+                ("has_byzantium", ctypes.c_uint8), ("dao_fork_support", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8 * 3), ("eip150_hash", ctypes.c_uint8 * 32)]
+
 
 # (name, restype, argtypes) for every symbol declared in include/gsv.h
 SIGNATURES = [
@@ -219,6 +259,14 @@ SIGNATURES = [
     ("gsv_ethash_full_batch", ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, _sz, _vp, _vp]),
     ("gsv_ethash_seal_batch", ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, _vp, _sz, _u64, _vp, _vp, _vp]),
     ("gsv_ctx_ethash_datasets", ctypes.c_int, [_vp, ctypes.POINTER(_sz)]),
+    ("gsv_block_header_hash_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    ("gsv_calc_difficulty_batch", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    ("gsv_ethash_verify_headers_batch", ctypes.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _u64, ctypes.c_int, _vp,
+                                                       _vp, _vp]),
+    ("gsv_block_header_work_bytes", _sz, [_sz]),
+    ("gsv_block_header_rules_dev", ctypes.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _u64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                  _vp, _vp, _vp, _vp, _vp]),
+    ("gsv_block_header_merge_dev", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     ("gsv_chunk_root_prepare", ctypes.c_int, [_vp, _vp, _sz]),
     ("gsv_bn256_pairing_prepare", ctypes.c_int, [_vp, _vp, _sz]),
     ("gsv_notary_prepare", ctypes.c_int, [_vp, _vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_uint32]),

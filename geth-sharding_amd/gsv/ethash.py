@@ -14,9 +14,12 @@ batched on the GPU.
     Ethash(test_mode).hashimotoFull             by block number, over the context's epoch datasets
     Ethash(test_mode).Seal / SealBatch          the search of mine (sealer.go:97-152), by block number
 
-The nonce is the number (Header.Nonce.Uint64()); types.BlockNonce is its big-endian bytes.  Not here:
-Header.HashNoNonce() from the header's RLP (Context.keccak256_batch makes it), the rest of verifyHeader, DAG
-and cache files on disk, remote mining / GetWork, and pre-generating the next epoch.
+    CalcDifficulty(config, time, parent_rlp)    consensus.go:297-459 over an RLP-encoded parent
+    Ethash(test_mode).VerifyHeaders / VerifyHeader   consensus.go:90-166, :223-285 over RLP-encoded headers
+
+The nonce is the number (Header.Nonce.Uint64()); types.BlockNonce is its big-endian bytes.  Not here: VerifyUncles,
+the known-block lookup of verifyHeaderWorker (the caller's database), Prepare / Finalize, DAG and cache files on
+disk, remote mining / GetWork, and pre-generating the next epoch.
 """
 from __future__ import annotations
 
@@ -43,6 +46,92 @@ class ErrInvalidPoW(ValueError):
 
 _ERRORS = {_lib.ST_INVALID_DIFFICULTY: ErrInvalidDifficulty, _lib.ST_INVALID_MIX_DIGEST: ErrInvalidMixDigest,
            _lib.ST_INVALID_POW: ErrInvalidPoW}
+
+
+class ErrBadHeaderRLP(ValueError):
+    """rlp: the header does not decode"""
+
+
+class ErrHeaderTooWide(ValueError):
+    """Difficulty or Time above 32 bytes, or Number above 8 (this library's bound, not the reference's)"""
+
+
+class ErrUnknownAncestor(ValueError):
+    """consensus.ErrUnknownAncestor (consensus/errors.go:24)"""
+
+
+class ErrExtraTooLong(ValueError):
+    """"extra-data too long" (consensus.go:225-227)"""
+
+
+class ErrFutureBlock(ValueError):
+    """consensus.ErrFutureBlock (consensus/errors.go:32)"""
+
+
+class ErrZeroBlockTime(ValueError):
+    """errZeroBlockTime (consensus.go:51)"""
+
+
+class ErrWrongDifficulty(ValueError):
+    """"invalid difficulty: have .., want .." (consensus.go:244-246)"""
+
+
+class ErrGasLimitCap(ValueError):
+    """"invalid gasLimit: have .., max .." (consensus.go:248-251)"""
+
+
+class ErrGasUsed(ValueError):
+    """"invalid gasUsed: have .., gasLimit .." (consensus.go:253-255)"""
+
+
+class ErrGasLimitBounds(ValueError):
+    """"invalid gas limit: have .., want .. += .." (consensus.go:258-266)"""
+
+
+class ErrInvalidNumber(ValueError):
+    """consensus.ErrInvalidNumber (consensus/errors.go:36)"""
+
+
+class ErrBadProDAOExtra(ValueError):
+    """misc.ErrBadProDAOExtra (consensus/misc/dao.go:32)"""
+
+
+class ErrBadNoDAOExtra(ValueError):
+    """misc.ErrBadNoDAOExtra (consensus/misc/dao.go:36)"""
+
+
+class ErrForkHash(ValueError):
+    """"homestead gas reprice fork: have .., want .." (consensus/misc/forks.go:36-39)"""
+
+
+_HEADER_ERRORS = dict(_ERRORS)
+_HEADER_ERRORS.update({
+    _lib.ST_BAD_RLP: ErrBadHeaderRLP, _lib.ST_HEADER_TOO_WIDE: ErrHeaderTooWide,
+    _lib.ST_UNKNOWN_ANCESTOR: ErrUnknownAncestor, _lib.ST_EXTRA_TOO_LONG: ErrExtraTooLong,
+    _lib.ST_FUTURE_BLOCK: ErrFutureBlock, _lib.ST_ZERO_BLOCK_TIME: ErrZeroBlockTime,
+    _lib.ST_WRONG_DIFFICULTY: ErrWrongDifficulty, _lib.ST_GAS_LIMIT_CAP: ErrGasLimitCap, _lib.ST_GAS_USED: ErrGasUsed,
+    _lib.ST_GAS_LIMIT_BOUNDS: ErrGasLimitBounds, _lib.ST_INVALID_NUMBER: ErrInvalidNumber,
+    _lib.ST_BAD_PRO_DAO_EXTRA: ErrBadProDAOExtra, _lib.ST_BAD_NO_DAO_EXTRA: ErrBadNoDAOExtra,
+    _lib.ST_FORK_HASH: ErrForkHash})
+
+
+def CalcDifficultyBatch(config, times, parent_rlps, ctx=None):
+    """(difficulties: list of int, status (n,)): CalcDifficulty(config, times[i], parent i) over RLP-encoded
+    parents.  A parent that does not decode has its decode status and difficulty None; a value of 2^256 or more
+    has ST_WRONG_DIFFICULTY and difficulty None."""
+    rows, st = (ctx or default_context()).calc_difficulty_batch(config, times, parent_rlps)
+    return [int.from_bytes(r.tobytes(), "big") if s == _lib.ST_OK else None for r, s in zip(rows, st)], st
+
+
+def CalcDifficulty(config, time: int, parent_rlp: bytes, ctx=None) -> int:
+    """CalcDifficulty(config, time, parent) (consensus.go:297-459), the parent as its RLP encoding.  Raises
+    ErrBadHeaderRLP / ErrHeaderTooWide for the parent, OverflowError for a value of 2^256 or more."""
+    vals, st = CalcDifficultyBatch(config, [int(time)], [parent_rlp], ctx)
+    if st[0] == _lib.ST_WRONG_DIFFICULTY:
+        raise OverflowError("ethash: the difficulty is 2^256 or more")
+    if st[0] != _lib.ST_OK:
+        raise _HEADER_ERRORS[int(st[0])](_lib.STATUS_STRINGS[int(st[0])])
+    return vals[0]
 
 
 def cacheSize(block: int) -> int:
@@ -250,6 +339,24 @@ class Ethash:
         if st[0] != _lib.ST_OK:
             return None
         return int(nonce[0]), mix[0].tobytes()
+
+    def VerifyHeaders(self, config, headers, seals=None, parent=None, now=None) -> np.ndarray:
+        """Ethash.VerifyHeaders (consensus.go:90-166): status (n,) uint8 per RLP-encoded header, the reference's
+        errors in the reference's order (include/gsv.h lists them).  seals: one flag per header, None = all;
+        parent: the RLP of header 0's parent, standing for chain.GetHeader(ParentHash, Number - 1); now: Unix
+        seconds, None = the clock.  The known-block short cut of verifyHeaderWorker is the caller's database and
+        is not here."""
+        if now is None:
+            import time
+            now = int(time.time())
+        return self.ctx.ethash_verify_headers_batch(config, headers, seals, parent, now, self.test_mode)
+
+    def VerifyHeader(self, config, header: bytes, parent: bytes, seal: bool = True, now=None) -> None:
+        """Ethash.VerifyHeader (consensus.go:71-84) of one RLP-encoded header against its parent: raises the
+        exception class of the reference's error"""
+        st = int(self.VerifyHeaders(config, [header], [seal], parent, now)[0])
+        if st != _lib.ST_OK:
+            raise _HEADER_ERRORS[st](_lib.STATUS_STRINGS[st])
 
     def VerifySeal(self, number: int, hash_no_nonce: bytes, nonce: int, mix_digest: bytes, difficulty: int) -> None:
         st = int(self.VerifySeals([number], [bytes(hash_no_nonce)], [nonce], [bytes(mix_digest)], [difficulty])[0])

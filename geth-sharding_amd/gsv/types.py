@@ -6,6 +6,8 @@
     SignTx(tx, signer, prv)      :56-63: signer.Hash(tx), crypto.Sign, tx.WithSignature
     SignTxBatch(txs, signer, keys)   batch form: per-item status codes
 
+    HeaderHashes(rlps)           Header.Hash() and Header.HashNoNonce() (core/types/block.go:99-122) over a batch
+
 The inverse, types.Sender over a batch, is Context.tx_sender_batch with the signer's kind and chain_id.
 Transactions travel as their RLP encoding (rlp.EncodeToBytes(tx)), signed or not; an unsigned
 NewTransaction carries V = R = S = 0.
@@ -74,4 +76,12 @@ def SignTx(tx_rlp: bytes, signer, prv, ctx=None) -> bytes:
     return signed[0]
 
 
-__all__ = ["EIP155Signer", "HomesteadSigner", "FrontierSigner", "SignTx", "SignTxBatch", "ErrInvalidKey", "ErrBadRLP"]
+def HeaderHashes(rlps, ctx=None):
+    """Header.Hash() and Header.HashNoNonce() of RLP-encoded headers (rlp.EncodeToBytes(header)): (hashes (n, 32)
+    uint8, hashes without nonce (n, 32) uint8, status (n,): ST_OK, ST_BAD_RLP where rlp.DecodeBytes refuses the
+    header, ST_HEADER_TOO_WIDE for a Difficulty or Time above 32 bytes or a Number above 8).  Both rows of a header
+    with ST_BAD_RLP are zeros."""
+    return (ctx or default_context()).block_header_hash_batch(rlps)
+
+
+__all__ = ["HeaderHashes", "EIP155Signer", "HomesteadSigner", "FrontierSigner", "SignTx", "SignTxBatch", "ErrInvalidKey", "ErrBadRLP"]

@@ -67,6 +67,11 @@
  *   gsv_ripemd160_batch        <- the ripemd160hash precompile's Run (core/vm/contracts.go:129-133)
  *                                 = common.LeftPadBytes(ripemd160.New().Write(input).Sum(nil), 32)
  *                                 (vendor/golang.org/x/crypto/ripemd160)
+ *   gsv_block_header_hash_batch <- Header.Hash() and Header.HashNoNonce() (core/types/block.go:99-122) over
+ *                                 RLP-encoded headers
+ *   gsv_calc_difficulty_batch  <- ethash.CalcDifficulty (consensus/ethash/consensus.go:297-459)
+ *   gsv_ethash_verify_headers_batch <- Ethash.VerifyHeaders (consensus/ethash/consensus.go:90-166): verifyHeaderWorker
+ *                                 and verifyHeader (:223-285) with uncle = false, VerifySeal included
  *
  * Conventions
  *   - Return value: GSV_SUCCESS (0) or a negative GSV_E_* API/HIP error. A bad ITEM never fails
@@ -134,6 +139,21 @@ extern "C" {
 #define GSV_ST_INVALID_POW 18        /* ethash errInvalidPoW           consensus/ethash/consensus.go:58 */
 #define GSV_ST_NONCE_NOT_FOUND 19    /* the sealer gave up after max_attempts nonces: not the reference's, whose
                                         mine() runs until it is aborted (consensus/ethash/sealer.go:110-118) */
+/* block headers (gsv_ethash_verify_headers_batch), in the order verifyHeaderWorker and verifyHeader test them */
+#define GSV_ST_HEADER_TOO_WIDE 20    /* a header that decodes, with Difficulty or Time above 32 bytes or Number above
+                                        8: not the reference's, whose big.Int fields have no bound */
+#define GSV_ST_UNKNOWN_ANCESTOR 21   /* consensus.ErrUnknownAncestor   consensus/errors.go:24, consensus.go:159-161 */
+#define GSV_ST_EXTRA_TOO_LONG 22     /* "extra-data too long"          consensus/ethash/consensus.go:225-227 */
+#define GSV_ST_FUTURE_BLOCK 23       /* consensus.ErrFutureBlock       consensus/errors.go:32, consensus.go:234-236 */
+#define GSV_ST_ZERO_BLOCK_TIME 24    /* ethash errZeroBlockTime        consensus.go:51, :238-240 */
+#define GSV_ST_WRONG_DIFFICULTY 25   /* "invalid difficulty"           consensus.go:242-246 */
+#define GSV_ST_GAS_LIMIT_CAP 26      /* "invalid gasLimit"             consensus.go:248-251 */
+#define GSV_ST_GAS_USED 27           /* "invalid gasUsed"              consensus.go:253-255 */
+#define GSV_ST_GAS_LIMIT_BOUNDS 28   /* "invalid gas limit"            consensus.go:258-266 */
+#define GSV_ST_INVALID_NUMBER 29     /* consensus.ErrInvalidNumber     consensus/errors.go:36, consensus.go:268-270 */
+#define GSV_ST_BAD_PRO_DAO_EXTRA 30  /* misc.ErrBadProDAOExtra         consensus/misc/dao.go:32, :58-61 */
+#define GSV_ST_BAD_NO_DAO_EXTRA 31   /* misc.ErrBadNoDAOExtra          consensus/misc/dao.go:36, :62-66 */
+#define GSV_ST_FORK_HASH 32          /* "homestead gas reprice fork"   consensus/misc/forks.go:36-39 */
 
 /* signer kinds for gsv_tx_sender_batch and gsv_tx_sign_batch (core/types/transaction_signing.go) */
 #define GSV_SIGNER_EIP155 0
@@ -202,6 +222,12 @@ int gsv_ctx_set_timing(gsv_ctx *ctx, int enable);
 #define GSV_K_ETHASH_SEARCH 21 /* ethash nonce search: one launch per gsv_ethash_search_dev */
 #define GSV_K_ETHASH_FINISH 22 /* the search's finish launch (the winners' rows): one per gsv_ethash_search_dev */
 #define GSV_K_PEAK 23
+/* Ids added behind GSV_K_PEAK (pinned like the six before it); gsv_ctx_kernel_time takes every id below
+ * GSV_K_SUMMIT. */
+#define GSV_K_BLOCK_HEADER 23 /* types.Header decode + Hash / HashNoNonce: one launch per call */
+#define GSV_K_BLOCK_RULES 24  /* verifyHeader's rules around the seal, or CalcDifficulty alone: one launch per call */
+#define GSV_K_BLOCK_MERGE 25  /* the merge of the pre-seal, seal and post-seal statuses: one launch per call */
+#define GSV_K_SUMMIT 26
 /* total milliseconds and launch count accumulated for kernel `kid` since the last reset */
 int gsv_ctx_kernel_time(gsv_ctx *ctx, int kid, double *total_ms, long *launches);
 int gsv_ctx_reset_timing(gsv_ctx *ctx);
@@ -637,10 +663,9 @@ int gsv_modexp_batch_dev(gsv_ctx *ctx, const uint8_t *d_in, size_t n, uint32_t b
 /* ---- ethash (consensus/ethash): hashimotoLight, VerifySeal, dataset items, hashimotoFull, Seal ----
  * What Ethash.VerifyHeaders (consensus.go:90) spends its time in: VerifySeal (consensus.go:463-501) runs
  * hashimotoLight (algorithm.go:375) per header over the epoch's verification cache.  An epoch is 30,000
- * blocks.  The sealing half follows below the light forms.  Not here: Header.HashNoNonce() from the header's
- * RLP (callers pass the 32-byte hash; gsv_keccak256_batch makes it from the 13-field RLP), the rest of
- * verifyHeader (timestamps, gas limits, CalcDifficulty), DAG and cache files on disk, remote mining / GetWork,
- * and pre-generating the next epoch.
+ * blocks.  The sealing half follows below the light forms, and behind it the block-header forms: the header's
+ * RLP, Header.Hash() / HashNoNonce(), CalcDifficulty and the whole of Ethash.VerifyHeaders.  Not here: DAG and
+ * cache files on disk, remote mining / GetWork, and pre-generating the next epoch.
  *
  * Host only, no context: cacheSize / datasetSize (algorithm.go:53-91) by the reference's formula for every
  * epoch (its 2,048-entry tables hold the same values), seedHash (algorithm.go:110-120) and generateCache
@@ -749,6 +774,114 @@ int gsv_ethash_seal_batch(gsv_ctx *ctx, const uint64_t *number, int test_mode, c
                           const uint8_t *difficulty32, const uint64_t *start_nonce, size_t n, uint64_t max_attempts,
                           uint64_t *nonce_out, uint8_t *mix32_out, uint8_t *status);
 int gsv_ctx_ethash_datasets(gsv_ctx *ctx, size_t *count);
+
+/* ---- block headers: Ethash.VerifyHeaders (consensus/ethash/consensus.go:90-166) over RLP-encoded headers ----
+ * A chain segment goes in, header i = rlp[off[i] .. off[i+1]) as rlp.EncodeToBytes(header), and one status per
+ * header comes out: verifyHeaderWorker (:152-166) and verifyHeader (:223-285) with uncle = false, the reference's
+ * errors in the reference's order.  eth/downloader feeds it 2,048 headers at a time.
+ *
+ * Decode, as rlp.DecodeBytes into types.Header (core/types/block.go:70-86): a list of exactly 15 items;
+ * ParentHash, UncleHash, Root, TxHash, ReceiptHash and MixDigest of exactly 32 bytes, Coinbase 20, Bloom 256,
+ * Nonce 8; Difficulty, Number and Time big integers and GasLimit, GasUsed uint64 (no leading zero byte, at most 8
+ * bytes for the two uint64); Extra a string of any length; every length in its shortest form and a single byte
+ * below 0x80 as itself; no element missing or left over, no byte behind the list, no length past the input.
+ * What the reference's decoder refuses is GSV_ST_BAD_RLP.  OURS, not the reference's: Difficulty and Time are
+ * held in 32 bytes and Number in 8, and a header that decodes with a wider one gets GSV_ST_HEADER_TOO_WIDE.
+ * An item of 2^32 bytes or more: GSV_E_TOO_LARGE from the host forms; the device forms give it GSV_ST_BAD_RLP
+ * unread.
+ *
+ * Hashes.  Hash() is Keccak-256 of the header's RLP (block.go:101-103).  HashNoNonce() (block.go:106-122) is
+ * Keccak-256 of the first 13 fields under a list head of their own: the payload without its last 42 bytes
+ * (MixDigest and Nonce).  Both rows are zeros for a header with GSV_ST_BAD_RLP.
+ *
+ * Parent (verifyHeaderWorker).  For i > 0 the parent is header i - 1 when Hash(i - 1) == ParentHash(i), whatever
+ * header i - 1's own status; else GSV_ST_UNKNOWN_ANCESTOR.  OURS: a header behind one that did not decode (BAD_RLP
+ * or HEADER_TOO_WIDE) is GSV_ST_UNKNOWN_ANCESTOR, since the reference never holds such a header in its slice.  For
+ * i = 0 the caller's parent_rlp (parent_len == 0: none) stands for chain.GetHeader(ParentHash, Number - 1): it is
+ * the parent when it decodes, its Hash() is ParentHash(0) and its Number is Number(0) - 1 in uint64; else
+ * GSV_ST_UNKNOWN_ANCESTOR.  The "known block" short cut (consensus.go:162-164) is a lookup in the caller's
+ * database and is NOT here: a caller who wants it drops the known headers' statuses.
+ *
+ * Checks, in verifyHeader's order; the first failure is the status:
+ *    1. len(Extra) > 32                                                  GSV_ST_EXTRA_TOO_LONG
+ *    2. Time > now + 15                                                  GSV_ST_FUTURE_BLOCK
+ *    3. Time <= parent.Time                                              GSV_ST_ZERO_BLOCK_TIME
+ *    4. CalcDifficulty(config, Time, parent) != Difficulty               GSV_ST_WRONG_DIFFICULTY
+ *    5. GasLimit > 2^63 - 1                                              GSV_ST_GAS_LIMIT_CAP
+ *    6. GasUsed > GasLimit                                               GSV_ST_GAS_USED
+ *    7. |int64(parent.GasLimit) - int64(GasLimit)| >= parent.GasLimit / 1024 or GasLimit < 5000
+ *                                                                        GSV_ST_GAS_LIMIT_BOUNDS
+ *       (the reference's two's-complement conversions: a parent above 2^63 wraps as int64() does)
+ *    8. Number - parent.Number != 1                                      GSV_ST_INVALID_NUMBER
+ *    9. where seals[i]: VerifySeal (the light form above)                GSV_ST_INVALID_DIFFICULTY / _MIX_DIGEST / _POW
+ *   10. misc.VerifyDAOHeaderExtraData (consensus/misc/dao.go:47-69)      GSV_ST_BAD_PRO_DAO_EXTRA / GSV_ST_BAD_NO_DAO_EXTRA
+ *   11. misc.VerifyForkHashes (consensus/misc/forks.go:30-43)            GSV_ST_FORK_HASH
+ * CalcDifficulty (consensus.go:297-459): the Frontier, Homestead or Byzantium rule by parent.Number + 1 (which does
+ * not wrap) against the configuration, in 256-bit arithmetic with a carry out.  An expected value of 2^256 or
+ * more equals no header's difficulty: GSV_ST_WRONG_DIFFICULTY, and the expected-difficulty row is 32 bytes of 0xFF.
+ *
+ * gsv_chain_config: the fields of params.ChainConfig (params/config.go:103-124) these rules read.  has_* is the
+ * big.Int pointer being non-nil.  `reserved` is zero. */
+typedef struct gsv_chain_config {
+    uint64_t homestead_block; /* HomesteadBlock */
+    uint64_t dao_fork_block;  /* DAOForkBlock */
+    uint64_t eip150_block;    /* EIP150Block */
+    uint64_t byzantium_block; /* ByzantiumBlock */
+    uint8_t has_homestead, has_dao_fork, has_eip150, has_byzantium;
+    uint8_t dao_fork_support; /* DAOForkSupport */
+    uint8_t reserved[3];
+    uint8_t eip150_hash[32]; /* EIP150Hash; all zero: not checked (misc/forks.go:37) */
+} gsv_chain_config;
+/* Host forms.  They stage, run and copy back; n == 0: success, nothing enqueued.
+ *   hash:       hash32 / hash_no_nonce32 (either may be NULL) row i, status[i] the decode status (GSV_ST_OK,
+ *               GSV_ST_BAD_RLP, GSV_ST_HEADER_TOO_WIDE).
+ *   difficulty: difficulty32 row i = CalcDifficulty(config, time[i], parent i) as 32 big-endian bytes, parent i =
+ *               parent_rlp[parent_off[i] .. parent_off[i+1]); status[i] the parent's decode status (row of zeros),
+ *               or GSV_ST_WRONG_DIFFICULTY with a row of 0xFF for a value of 2^256 or more.  time[i] may lie
+ *               before the parent's time (big.Int.Div floors).
+ *   headers:    the whole of VerifyHeaders.  seals: n bytes, NULL = all true.  now: Unix seconds, at most 2^63
+ *               (else GSV_E_INVALID_ARG).  test_mode as in the seal forms.  hash32 (NULL or n rows): Hash() of each
+ *               header.  expected_difficulty32 (NULL or n rows): what check 4 compared against, zeros for a header
+ *               that failed before it.  The flow: decode and rules on the device; Number and the pre-seal status
+ *               come back; the headers with seals[i] that have passed so far (the reference never runs VerifySeal
+ *               behind an earlier failure) are grouped by epoch through the context's cache list and run through the
+ *               light kernel, as gsv_ethash_verify_seal_batch does; the three statuses are merged on the device. */
+int gsv_block_header_hash_batch(gsv_ctx *ctx, const uint8_t *rlp, const uint64_t *off, size_t n, uint8_t *hash32,
+                                uint8_t *hash_no_nonce32, uint8_t *status);
+int gsv_calc_difficulty_batch(gsv_ctx *ctx, const gsv_chain_config *config, const uint64_t *time,
+                              const uint8_t *parent_rlp, const uint64_t *parent_off, size_t n, uint8_t *difficulty32,
+                              uint8_t *status);
+int gsv_ethash_verify_headers_batch(gsv_ctx *ctx, const gsv_chain_config *config, const uint8_t *rlp,
+                                    const uint64_t *off, size_t n, const uint8_t *parent_rlp, size_t parent_len,
+                                    const uint8_t *seals, uint64_t now, int test_mode, uint8_t *status, uint8_t *hash32,
+                                    uint8_t *expected_difficulty32);
+/* Device-resident forms.  Both only enqueue on `stream` (NULL = the context stream): no allocation, no
+ * synchronisation, no prepare call (the configuration and `now` travel as kernel arguments), capturable; n == 0:
+ * success, nothing enqueued.  The caller runs gsv_ethash_verify_seal_batch_dev between them over one epoch's cache.
+ *   rules: two launches, k_block_header (GSV_K_BLOCK_HEADER) and k_block_header_rules (GSV_K_BLOCK_RULES).  d_rlp and
+ *          d_off as in gsv_keccak256_batch_dev; d_parent_rlp parent_len bytes in HBM (parent_len == 0: no parent,
+ *          the pointer is not read).  d_work: gsv_block_header_work_bytes(n) bytes of the caller's, 16-byte
+ *          aligned: the records the two launches hand each other.  It writes the four arrays the seal call takes:
+ *          d_hash_no_nonce32 (4-byte aligned), d_nonce (8-byte aligned; Header.Nonce.Uint64()), d_mix32 and
+ *          d_difficulty32 (any alignment), zeros for a header that did not decode; d_pre_status and
+ *          d_post_status (checks 1-8 and the link; checks 10-11); and, each NULL or n rows, d_hash32 (any
+ *          alignment), d_number (8-byte aligned) and d_expected_difficulty32 (any alignment).  The kernels read no
+ *          byte outside d_rlp[d_off[0] .. d_off[n]) and the parent but for the other bytes of the aligned dwords
+ *          that hold an item's first and last byte.
+ *   merge: one launch (GSV_K_BLOCK_MERGE).  d_status[i] = d_pre_status[i] if it is not GSV_ST_OK; else
+ *          d_seal_status[i] where d_seal_status is not NULL and d_seals is NULL or d_seals[i] != 0, if it is not
+ *          GSV_ST_OK; else d_post_status[i].
+ * GSV_E_INVALID_ARG: a NULL context, configuration or required array, a misaligned array, now above 2^63, n or
+ * parent_len above 2^31 - 1. */
+size_t gsv_block_header_work_bytes(size_t n);
+int gsv_block_header_rules_dev(gsv_ctx *ctx, const gsv_chain_config *config, const uint8_t *d_rlp,
+                               const uint64_t *d_off, size_t n, const uint8_t *d_parent_rlp, size_t parent_len,
+                               uint64_t now, uint8_t *d_work, uint8_t *d_hash_no_nonce32, uint64_t *d_nonce,
+                               uint8_t *d_mix32, uint8_t *d_difficulty32, uint8_t *d_pre_status, uint8_t *d_post_status,
+                               uint8_t *d_hash32, uint64_t *d_number, uint8_t *d_expected_difficulty32, void *stream);
+int gsv_block_header_merge_dev(gsv_ctx *ctx, const uint8_t *d_pre_status, const uint8_t *d_seal_status,
+                               const uint8_t *d_seals, const uint8_t *d_post_status, size_t n, uint8_t *d_status,
+                               void *stream);
 
 /* ---- synthetic signed workload (bench / test data generator; signing is not on the path) ----
  * key_i, msg_i, nonce_i = Keccak256(le64(seed) || le64(i) || "key"/"msg"/"nce"), key and nonce
