@@ -1,6 +1,7 @@
 // Internals of the C ABI of libgsv.so (include/gsv.h), shared by its translation units:
 //   gsv_ctx.hip      context, streams, kernel timing, staging arena, the cache of prepared shapes
 //   gsv_batch.hip    stateless batches: Keccak, ecrecover and its precompile, bn256 add / mul, senders
+//   gsv_hash.hip     SHA-256, RIPEMD-160, and the host form the three hashes share (hash_host)
 //   gsv_ecies.hip    ecies.Encrypt / Decrypt: the launch chains around the ladder
 //   gsv_txsign.hip   types.SignTx: the launch chain around the signature kernel
 //   gsv_modexp.hip   the modexp precompile: host grouping by modulus width, one launch per class
@@ -10,9 +11,12 @@
 //   gsv_pairing.hip  BN254 pairing check
 //   gsv_notary.hip   notary validation, shard partition + RCCL all-gather
 //   gsv_proposer.hip blob codec (Serialize / Deserialize), createCollation
+// and two headers free of HIP: staging.h (the staged buffers of every host form, declared once) and
+// offset_table.h (the rule for a caller's offset table, its rebased copy, fixed records).
 //
 // Host-pointer entry points stage through a grow-only device arena on the context's stream and are
-// synchronous.  *_dev entry points take HBM-resident buffers and the caller's stream and only
+// synchronous: check the arguments (offset_table.h), declare the *Stage (staging.h), open a Staged (below),
+// copy in, call the _dev form, copy out, finish.  *_dev entry points take HBM-resident buffers and the caller's stream and only
 // enqueue: they never allocate and never synchronize, so they can be captured into a HIP graph.
 // Everything a *_dev call derives from its host-side arguments (trie plans per body length, device
 // copies of offset tables, pairing lane tables, its workspace) lives in a PREPARED SHAPE built by the
@@ -35,6 +39,7 @@
 
 #include "chunk_root.h"
 #include "gsv_internal.h"
+#include "offset_table.h"
 #include "staging.h"
 
 struct ncclComm;  // rccl.h (gsv_notary.hip)
@@ -247,22 +252,80 @@ inline int hip_err(hipError_t e) { return e == hipSuccess ? GSV_SUCCESS : GSV_E_
         if (_e != hipSuccess) return GSV_E_HIP;    \
     } while (0)
 
-// The staged secret keys of a host form: overwritten on the context stream, and the stream waited
-// for, on every way out of the scope that follows the copy-in (HIPCHK's early returns included).
-// finish() is the success path's last step and reports the two calls' outcome.
-struct SecretWipe {
+#define GSVCHK(x)               \
+    do {                        \
+        int _rc = (x);          \
+        if (_rc) return _rc;    \
+    } while (0)
+
+// the stream of a *_dev call: the caller's, or the context's
+inline hipStream_t stream_of(gsv_ctx* c, void* stream) { return stream ? (hipStream_t)stream : c->stream; }
+// the kernels index a batch with 32 bits
+inline bool batch_too_long(size_t n) { return n > 0xFFFFFFFFull; }
+
+int arena_reserve(gsv_ctx* c, size_t bytes);
+
+// One host form's turn at the staging arena, opened after the argument checks: holds the context's lock (its
+// own, or one the caller holds already and may drop and retake between two turns), sets the device and
+// reserves what the stage declared.  `rc` is the outcome of that; the entry point returns it when nonzero.
+// Then in() and out() copy between host memory and a staged buffer on the context's stream, and finish()
+// waits for the stream.  A copy is as long as the buffer was declared (Buf::bytes) or a stated shorter
+// length; one that would pass the buffer's end fails with GSV_E_INVALID_ARG and enqueues nothing.  An absent
+// buffer (an optional output not asked for) and a copy of no bytes are skipped.
+// A pointer into the arena is bound by s(buf), and only after the call's LAST reservation: arena_reserve may
+// move the arena, and a form with a per-call shape reserves in shape_temp (kWithShape leaves it to that).
+// secret() names the region that holds key material from the next copy on: [key.off, key.off + key.bytes), or
+// [0, end) of a stage that puts every secret first.  It is overwritten on the context's stream, and the stream
+// waited for, on every way out that follows (GSVCHK's and HIPCHK's early returns included); finish() is the
+// success path's last step and reports the outcome of both calls.
+struct Staged {
+    enum Reserve { kNow, kWithShape };
     gsv_ctx* c;
-    uint8_t* p;
-    size_t bytes;
-    bool done = false;
+    std::unique_lock<std::mutex> own;  // empty when the caller's lock was adopted
+    int rc;
+    size_t wipe_off = 0, wipe_bytes = 0;
+
+    Staged(gsv_ctx* c_, const Layout& L, Reserve r = kNow) : c(c_), own(c_->mu), rc(open(L, r)) {}
+    Staged(gsv_ctx* c_, const Layout& L, std::unique_lock<std::mutex>& held) : c(c_), rc(open(L, kNow)) {
+        if (!held.owns_lock()) rc = GSV_E_INVALID_ARG;
+    }
+    Staged(const Staged&) = delete;
+    Staged& operator=(const Staged&) = delete;
+    ~Staged() {
+        if (wipe_bytes) finish();
+    }
+
+    template <typename T>
+    T* operator()(const Buf<T>& b) const { return b(c->arena); }
+    template <typename T>
+    int in(const Buf<T>& b, const void* src) { return in(b, src, b.bytes); }
+    template <typename T>
+    int in(const Buf<T>& b, const void* src, size_t bytes) {
+        if (b.off == kAbsent || !bytes) return GSV_SUCCESS;
+        if (bytes > b.bytes) return GSV_E_INVALID_ARG;
+        return hip_err(hipMemcpyAsync(c->arena + b.off, src, bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    template <typename T>
+    int out(void* dst, const Buf<T>& b) { return out(dst, b, b.bytes); }
+    template <typename T>
+    int out(void* dst, const Buf<T>& b, size_t bytes) {
+        if (b.off == kAbsent || !bytes) return GSV_SUCCESS;
+        if (bytes > b.bytes) return GSV_E_INVALID_ARG;
+        return hip_err(hipMemcpyAsync(dst, c->arena + b.off, bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    void secret(const B8& key) { wipe_off = key.off, wipe_bytes = key.bytes; }
+    void secret(size_t end) { wipe_off = 0, wipe_bytes = end; }
     int finish() {
-        done = true;
-        hipError_t a = hipMemsetAsync(p, 0, bytes, c->stream);
+        hipError_t a = wipe_bytes ? hipMemsetAsync(c->arena + wipe_off, 0, wipe_bytes, c->stream) : hipSuccess;
+        wipe_bytes = 0;
         hipError_t b = hipStreamSynchronize(c->stream);
         return hip_err(a != hipSuccess ? a : b);
     }
-    ~SecretWipe() {
-        if (!done) finish();
+
+private:
+    int open(const Layout& L, Reserve r) {
+        HIPCHK(hipSetDevice(c->device));
+        return r == kNow ? arena_reserve(c, L.n) : GSV_SUCCESS;
     }
 };
 
@@ -277,7 +340,6 @@ hipEvent_t take_event(gsv_ctx* c);
 // timer hooks for multi-launch paths (chunk-root levels, pairing stages)
 void hook_begin(void* ctx, int kid);
 void hook_end(void* ctx, int kid);
-int arena_reserve(gsv_ctx* c, size_t bytes);
 int device_cus(int device);
 int shape_materialize(Shape& s, size_t bytes, uint8_t* carve = nullptr, int ninst = 1);
 Shape* shape_find(gsv_ctx* c, uint64_t kind, const std::vector<uint64_t>& key);
@@ -285,8 +347,11 @@ void shape_insert(gsv_ctx* c, std::unique_ptr<Shape> s);
 int shape_pick(Shape& s, hipStream_t st, bool cap);
 int shape_side_init(gsv_ctx* c, Shape& s);
 int shape_side_borrow(gsv_ctx* c, Shape& s);
+// ---- gsv_hash.hip: the host form of gsv_keccak256_batch, gsv_sha256_batch and gsv_ripemd160_batch
+typedef hipError_t (*hash_launch)(const uint8_t*, const uint64_t*, uint32_t, uint8_t*, hipStream_t);
+int hash_host(gsv_ctx* c, int kid, hash_launch launch, const uint8_t* data, const uint64_t* off, size_t n,
+              uint8_t* out32);
 // ---- gsv_trie.hip: chunk roots of bodies grouped by length, shared with the notary
-constexpr uint64_t MAX_BODY = 1ull << 20;  // collationSizelimit (sharding/collation.go:45)
 int chunk_prepare(gsv_ctx* c, Shape& s, ChunkLaunch& cl, Layout& L, const uint64_t* start, const uint64_t* end,
                   size_t n, uint64_t max_len);
 int chunk_run(gsv_ctx* c, const Shape& s, const ChunkLaunch& cl, const uint8_t* d_bodies, uint8_t* d_roots,

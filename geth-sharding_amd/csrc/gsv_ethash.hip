@@ -170,7 +170,6 @@ int host_batch_locked(gsv_ctx* c, std::unique_lock<std::mutex>& lk, const uint64
         int rc = full ? epoch_dataset(c, lk, g.first, test, sz, &d_dataset)
                       : epoch_cache(c, lk, g.first, test, sz, &d_cache);
         if (rc) return rc;
-        HIPCHK(hipSetDevice(c->device));
         h.resize(m * 32);
         nn.resize(m);
         a.resize(m * 32);
@@ -187,28 +186,25 @@ int host_batch_locked(gsv_ctx* c, std::unique_lock<std::mutex>& lk, const uint64
         }
         Layout L;
         const EthashStage p(L, m, verify);
-        rc = arena_reserve(c, L.n);
-        if (rc) return rc;
-        uint8_t *d_h = p.hash(c->arena), *d_a = p.a(c->arena), *d_b = p.b(c->arena), *d_st = p.st(c->arena);
-        uint64_t* d_n = p.nonce(c->arena);
-        HIPCHK(hipMemcpyAsync(d_h, h.data(), m * 32, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(d_n, nn.data(), m * 8, hipMemcpyHostToDevice, c->stream));
+        Staged s(c, L, lk);
+        if (s.rc) return s.rc;
+        GSVCHK(s.in(p.hash, h.data()));
+        GSVCHK(s.in(p.nonce, nn.data()));
         if (verify) {
-            HIPCHK(hipMemcpyAsync(d_a, a.data(), m * 32, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(d_b, b.data(), m * 32, hipMemcpyHostToDevice, c->stream));
-            rc = gsv_ethash_verify_seal_batch_dev(c, d_cache, sz.cache_bytes, sz.dataset_bytes, d_h, d_n, d_a, d_b, m,
-                                                  d_st, c->stream);
-            if (rc) return rc;
-            HIPCHK(hipMemcpyAsync(st.data(), d_st, m, hipMemcpyDeviceToHost, c->stream));
+            GSVCHK(s.in(p.a, a.data()));
+            GSVCHK(s.in(p.b, b.data()));
+            GSVCHK(gsv_ethash_verify_seal_batch_dev(c, d_cache, sz.cache_bytes, sz.dataset_bytes, s(p.hash), s(p.nonce),
+                                                    s(p.a), s(p.b), m, s(p.st), c->stream));
+            GSVCHK(s.out(st.data(), p.st));
         } else {
-            rc = full ? gsv_ethash_full_batch_dev(c, d_dataset, sz.dataset_bytes, d_h, d_n, m, d_a, d_b, c->stream)
-                      : gsv_ethash_light_batch_dev(c, d_cache, sz.cache_bytes, sz.dataset_bytes, d_h, d_n, m, d_a, d_b,
-                                                   c->stream);
-            if (rc) return rc;
-            HIPCHK(hipMemcpyAsync(a.data(), d_a, m * 32, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(b.data(), d_b, m * 32, hipMemcpyDeviceToHost, c->stream));
+            GSVCHK(full ? gsv_ethash_full_batch_dev(c, d_dataset, sz.dataset_bytes, s(p.hash), s(p.nonce), m, s(p.a),
+                                                    s(p.b), c->stream)
+                        : gsv_ethash_light_batch_dev(c, d_cache, sz.cache_bytes, sz.dataset_bytes, s(p.hash), s(p.nonce),
+                                                     m, s(p.a), s(p.b), c->stream));
+            GSVCHK(s.out(a.data(), p.a));
+            GSVCHK(s.out(b.data(), p.b));
         }
-        HIPCHK(hipStreamSynchronize(c->stream));
+        GSVCHK(s.finish());
         for (size_t k = 0; k < m; k++) {
             const size_t i = items[k];
             if (verify) {
@@ -253,7 +249,7 @@ int gsv_ethash_dataset_items_dev(gsv_ctx* c, const uint8_t* d_cache, uint64_t ca
         return GSV_E_INVALID_ARG;
     if (count == 0) return GSV_SUCCESS;
     if (!d_out64 || ((uintptr_t)d_out64 & 15) || count > 0xFFFFFFFFull) return GSV_E_INVALID_ARG;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     KTimer t(c, GSV_K_ETHASH_ITEMS, st);
     return hip_err(gsv::launch_ethash_items(d_cache, cache_bytes, (uint32_t)first, (uint32_t)count, d_out64, st));
 }
@@ -264,7 +260,7 @@ int gsv_ethash_light_batch_dev(gsv_ctx* c, const uint8_t* d_cache, uint64_t cach
     if (!c || !cache_ok(d_cache, cache_bytes) || !dataset_ok(dataset_bytes) || n > MAX_N) return GSV_E_INVALID_ARG;
     if (n == 0) return GSV_SUCCESS;
     if (!seed_ok(d_hash32, d_nonce) || !d_mix32 || !d_result32) return GSV_E_INVALID_ARG;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     KTimer t(c, GSV_K_ETHASH_LIGHT, st);
     return hip_err(gsv::launch_ethash_light(d_cache, cache_bytes, dataset_bytes, d_hash32, d_nonce, (uint32_t)n,
                                             d_mix32, d_result32, st));
@@ -276,7 +272,7 @@ int gsv_ethash_verify_seal_batch_dev(gsv_ctx* c, const uint8_t* d_cache, uint64_
     if (!c || !cache_ok(d_cache, cache_bytes) || !dataset_ok(dataset_bytes) || n > MAX_N) return GSV_E_INVALID_ARG;
     if (n == 0) return GSV_SUCCESS;
     if (!seed_ok(d_hash32, d_nonce) || !d_mix32 || !d_difficulty32 || !d_status) return GSV_E_INVALID_ARG;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     KTimer t(c, GSV_K_ETHASH_LIGHT, st);
     return hip_err(gsv::launch_ethash_verify(d_cache, cache_bytes, dataset_bytes, d_hash32, d_nonce, d_mix32,
                                              d_difficulty32, (uint32_t)n, d_status, st));
@@ -300,7 +296,7 @@ int gsv_ethash_full_batch_dev(gsv_ctx* c, const uint8_t* d_dataset, uint64_t dat
     if (!c || !full_dataset_ok(d_dataset, dataset_bytes) || n > MAX_N) return GSV_E_INVALID_ARG;
     if (n == 0) return GSV_SUCCESS;
     if (!seed_ok(d_hash32, d_nonce) || !d_mix32 || !d_result32) return GSV_E_INVALID_ARG;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     KTimer t(c, GSV_K_ETHASH_FULL, st);
     return hip_err(gsv::launch_ethash_full(d_dataset, dataset_bytes, d_hash32, d_nonce, (uint32_t)n, d_mix32,
                                            d_result32, st));
@@ -312,7 +308,7 @@ int gsv_ethash_verify_seal_full_batch_dev(gsv_ctx* c, const uint8_t* d_dataset, 
     if (!c || !full_dataset_ok(d_dataset, dataset_bytes) || n > MAX_N) return GSV_E_INVALID_ARG;
     if (n == 0) return GSV_SUCCESS;
     if (!seed_ok(d_hash32, d_nonce) || !d_mix32 || !d_difficulty32 || !d_status) return GSV_E_INVALID_ARG;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     KTimer t(c, GSV_K_ETHASH_FULL, st);
     return hip_err(gsv::launch_ethash_verify_full(d_dataset, dataset_bytes, d_hash32, d_nonce, d_mix32,
                                                   d_difficulty32, (uint32_t)n, d_status, st));
@@ -328,7 +324,7 @@ int gsv_ethash_search_dev(gsv_ctx* c, const uint8_t* d_dataset, uint64_t dataset
     if (!seed_ok(d_hash32, d_start) || !d_difficulty32 || !d_offset || ((uintptr_t)d_offset & 3) || !d_nonce_out ||
         ((uintptr_t)d_nonce_out & 7) || !d_mix32 || !d_result32 || !d_found)
         return GSV_E_INVALID_ARG;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     // A 32-bit fill, not hipMemsetAsync(.., 0xFF, 4 n).  An observation, seen in one test run and not traced
     // to its cause: with the byte form captured into a graph and d_offset at 4 mod 16, the three words in front
     // of the first 16-byte boundary read zero after the replay, so those headers "won" at offset 0; the same
@@ -387,7 +383,6 @@ int gsv_ethash_seal_batch(gsv_ctx* c, const uint64_t* number, int test_mode, con
         const uint8_t* d_dataset = nullptr;
         rc = epoch_dataset(c, lk, g.first, test, sz, &d_dataset);
         if (rc) return rc;
-        HIPCHK(hipSetDevice(c->device));
         for (uint64_t tried = 0; tried < max_attempts && !items.empty();) {
             const eth::SealRound round = eth::seal_round(items.size(), max_attempts - tried);
             std::vector<uint32_t> keep_items;
@@ -407,19 +402,18 @@ int gsv_ethash_seal_batch(gsv_ctx* c, const uint64_t* number, int test_mode, con
                 }
                 Layout L;
                 const EthashSealStage p(L, m);
-                rc = arena_reserve(c, L.n);
-                if (rc) return rc;
-                HIPCHK(hipMemcpyAsync(p.hash(c->arena), h.data(), m * 32, hipMemcpyHostToDevice, c->stream));
-                HIPCHK(hipMemcpyAsync(p.diff(c->arena), d.data(), m * 32, hipMemcpyHostToDevice, c->stream));
-                HIPCHK(hipMemcpyAsync(p.start(c->arena), start.data(), m * 8, hipMemcpyHostToDevice, c->stream));
-                rc = gsv_ethash_search_dev(c, d_dataset, sz.dataset_bytes, p.hash(c->arena), p.diff(c->arena),
-                                           p.start(c->arena), m, round.span, p.offset(c->arena), p.nonce(c->arena),
-                                           p.mix(c->arena), p.result(c->arena), p.found(c->arena), c->stream);
-                if (rc) return rc;
-                HIPCHK(hipMemcpyAsync(won.data(), p.nonce(c->arena), m * 8, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(hipMemcpyAsync(mix.data(), p.mix(c->arena), m * 32, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(hipMemcpyAsync(found.data(), p.found(c->arena), m, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(hipStreamSynchronize(c->stream));
+                Staged s(c, L, lk);
+                if (s.rc) return s.rc;
+                GSVCHK(s.in(p.hash, h.data()));
+                GSVCHK(s.in(p.diff, d.data()));
+                GSVCHK(s.in(p.start, start.data()));
+                GSVCHK(gsv_ethash_search_dev(c, d_dataset, sz.dataset_bytes, s(p.hash), s(p.diff), s(p.start), m,
+                                             round.span, s(p.offset), s(p.nonce), s(p.mix), s(p.result), s(p.found),
+                                             c->stream));
+                GSVCHK(s.out(won.data(), p.nonce));
+                GSVCHK(s.out(mix.data(), p.mix));
+                GSVCHK(s.out(found.data(), p.found));
+                GSVCHK(s.finish());
                 for (size_t k = 0; k < m; k++) {
                     const uint32_t i = items[at + k];
                     if (found[k]) {

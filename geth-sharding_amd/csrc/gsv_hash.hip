@@ -1,6 +1,7 @@
 // The Merkle-Damgard hashes of the C ABI (gsv_ctx.h): SHA-256 and RIPEMD-160 over batches of
 // variable-length messages, the sha256hash and ripemd160hash precompiles (core/vm/contracts.go:104-133).
-// The conventions are gsv_keccak256_batch's (gsv_batch.hip), whose staging layout the host forms share.
+// The host forms of these two and of gsv_keccak256_batch (gsv_batch.hip) are one routine, hash_host: a table of
+// any item length (offset_table.h), the bytes and the rebased table staged in a KeccakStage, one launch.
 #include <vector>
 
 #include "gsv_ctx.h"
@@ -9,46 +10,43 @@ using namespace gsv::api;
 
 namespace {
 
-typedef hipError_t (*md_launch)(const uint8_t*, const uint64_t*, uint32_t, uint8_t*, hipStream_t);
-
-int md_batch_dev(gsv_ctx* c, int kid, md_launch launch, const uint8_t* d_data, const uint64_t* d_off, size_t n,
+int md_batch_dev(gsv_ctx* c, int kid, hash_launch launch, const uint8_t* d_data, const uint64_t* d_off, size_t n,
                  uint8_t* d_out32, void* stream) {
-    if (!c || (n && (!d_off || !d_out32)) || n > 0xFFFFFFFFull) return GSV_E_INVALID_ARG;
+    if (!c || (n && (!d_off || !d_out32)) || batch_too_long(n)) return GSV_E_INVALID_ARG;
     if (n == 0) return GSV_SUCCESS;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     KTimer t(c, kid, st);
     return hip_err(launch(d_data, d_off, (uint32_t)n, d_out32, st));
 }
 
-int md_batch(gsv_ctx* c, int kid, md_launch launch, const uint8_t* data, const uint64_t* off, size_t n,
-             uint8_t* out32) {
-    if (!c || (n && (!off || !out32)) || n > 0xFFFFFFFFull) return GSV_E_INVALID_ARG;
+}  // namespace
+
+namespace gsv {
+namespace api {
+
+int hash_host(gsv_ctx* c, int kid, hash_launch launch, const uint8_t* data, const uint64_t* off, size_t n,
+              uint8_t* out32) {
+    if (!c || (n && (!off || !out32)) || batch_too_long(n)) return GSV_E_INVALID_ARG;
     if (n == 0) return GSV_SUCCESS;
-    for (size_t i = 0; i < n; i++)  // the kernels trust off[i] <= off[i+1]
-        if (off[i + 1] < off[i]) return GSV_E_INVALID_ARG;
-    if (off[n] > off[0] && !data) return GSV_E_INVALID_ARG;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    size_t bytes = off[n] - off[0];
+    GSVCHK(table_check(data, off, n));  // the kernels trust off[i] <= off[i+1]
+    const size_t bytes = off[n] - off[0];
+    const std::vector<uint64_t> rel = table_rebase(off, n);
     Layout L;
     const KeccakStage p(L, bytes, n);
-    int rc = arena_reserve(c, L.n);
-    if (rc) return rc;
-    uint8_t* d_data = p.data(c->arena);
-    uint64_t* d_off = p.off(c->arena);
-    uint8_t* d_out = p.out(c->arena);
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
-    if (bytes) HIPCHK(hipMemcpyAsync(d_data, data + off[0], bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_off, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    rc = md_batch_dev(c, kid, launch, d_data, d_off, n, d_out, c->stream);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out32, d_out, n * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return GSV_SUCCESS;
+    Staged s(c, L);
+    if (s.rc) return s.rc;
+    GSVCHK(s.in(p.data, data + off[0], bytes));
+    GSVCHK(s.in(p.off, rel.data()));
+    {
+        KTimer t(c, kid, c->stream);
+        HIPCHK(launch(s(p.data), s(p.off), (uint32_t)n, s(p.out), c->stream));
+    }
+    GSVCHK(s.out(out32, p.out));
+    return s.finish();
 }
 
-}  // namespace
+}  // namespace api
+}  // namespace gsv
 
 extern "C" {
 
@@ -58,7 +56,7 @@ int gsv_sha256_batch_dev(gsv_ctx* c, const uint8_t* d_data, const uint64_t* d_of
 }
 
 int gsv_sha256_batch(gsv_ctx* c, const uint8_t* data, const uint64_t* off, size_t n, uint8_t* out32) {
-    return md_batch(c, GSV_K_SHA256, gsv::launch_sha256, data, off, n, out32);
+    return hash_host(c, GSV_K_SHA256, gsv::launch_sha256, data, off, n, out32);
 }
 
 int gsv_ripemd160_batch_dev(gsv_ctx* c, const uint8_t* d_data, const uint64_t* d_off, size_t n, uint8_t* d_out32,
@@ -67,7 +65,7 @@ int gsv_ripemd160_batch_dev(gsv_ctx* c, const uint8_t* d_data, const uint64_t* d
 }
 
 int gsv_ripemd160_batch(gsv_ctx* c, const uint8_t* data, const uint64_t* off, size_t n, uint8_t* out32) {
-    return md_batch(c, GSV_K_RIPEMD160, gsv::launch_ripemd160, data, off, n, out32);
+    return hash_host(c, GSV_K_RIPEMD160, gsv::launch_ripemd160, data, off, n, out32);
 }
 
 }  // extern "C"

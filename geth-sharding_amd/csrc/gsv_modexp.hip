@@ -10,19 +10,17 @@ static_assert(mdx::MAX_LEN == GSV_MODEXP_MAX_LEN, "the cap of gsv.h");
 
 namespace {
 
-// headers, statuses and output offsets of a batch; false for a table that runs backwards
-bool layout(const uint8_t* in, const uint64_t* off, size_t n, std::vector<mdx::Header>* hdr, uint64_t* out_off,
+// headers, statuses and output offsets of a batch whose table has passed table_check
+void layout(const uint8_t* in, const uint64_t* off, size_t n, std::vector<mdx::Header>* hdr, uint64_t* out_off,
             uint8_t* status) {
     out_off[0] = 0;
     for (size_t i = 0; i < n; i++) {
-        if (off[i + 1] < off[i]) return false;
         const mdx::Header h = mdx::parse_header(in + off[i], off[i + 1] - off[i]);
         const bool over = mdx::too_long(h);
         status[i] = over ? GSV_ST_MODEXP_TOO_LONG : GSV_ST_OK;
         out_off[i + 1] = out_off[i] + (over ? 0 : h.mod_len);
         if (hdr) hdr->push_back(h);
     }
-    return true;
 }
 
 }  // namespace
@@ -33,10 +31,9 @@ int gsv_modexp_output_layout(const uint8_t* in, const uint64_t* off, size_t n, u
     if (!out_off || (n && (!off || !status))) return GSV_E_INVALID_ARG;
     out_off[0] = 0;
     if (n == 0) return GSV_SUCCESS;
-    for (size_t i = 0; i < n; i++)
-        if (off[i + 1] < off[i]) return GSV_E_INVALID_ARG;
-    if (off[n] != off[0] && !in) return GSV_E_INVALID_ARG;
-    return layout(in, off, n, nullptr, out_off, status) ? GSV_SUCCESS : GSV_E_INVALID_ARG;
+    GSVCHK(table_check(in, off, n));
+    layout(in, off, n, nullptr, out_off, status);
+    return GSV_SUCCESS;
 }
 
 size_t gsv_modexp_work_bytes(size_t n, uint32_t base_len, uint32_t exp_len, uint32_t mod_len) {
@@ -46,28 +43,26 @@ size_t gsv_modexp_work_bytes(size_t n, uint32_t base_len, uint32_t exp_len, uint
 
 int gsv_modexp_batch_dev(gsv_ctx* c, const uint8_t* d_in, size_t n, uint32_t base_len, uint32_t exp_len,
                          uint32_t mod_len, uint8_t* d_out, uint8_t* d_work, void* stream) {
-    if (!c || base_len > mdx::MAX_LEN || exp_len > mdx::MAX_LEN || mod_len > mdx::MAX_LEN || n > 0xFFFFFFFFull)
+    if (!c || base_len > mdx::MAX_LEN || exp_len > mdx::MAX_LEN || mod_len > mdx::MAX_LEN || batch_too_long(n))
         return GSV_E_INVALID_ARG;
     if (n == 0 || mod_len == 0) return GSV_SUCCESS;
     if (!d_in || !d_out || (mdx::work_bytes(n, mod_len) && (!d_work || ((uintptr_t)d_work & 3))))
         return GSV_E_INVALID_ARG;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     KTimer t(c, GSV_K_MODEXP, st);
     return hip_err(gsv::launch_modexp(d_in, (uint32_t)n, base_len, exp_len, mod_len, d_out, d_work, st));
 }
 
 int gsv_modexp_batch(gsv_ctx* c, const uint8_t* in, const uint64_t* off, size_t n, uint8_t* out,
                      const uint64_t* out_off, uint8_t* status) {
-    if (!c || n > 0xFFFFFFFFull || (n && (!off || !out_off || !status))) return GSV_E_INVALID_ARG;
+    if (!c || batch_too_long(n) || (n && (!off || !out_off || !status))) return GSV_E_INVALID_ARG;
     if (n == 0) return GSV_SUCCESS;
-    for (size_t i = 0; i < n; i++)
-        if (off[i + 1] < off[i]) return GSV_E_INVALID_ARG;
-    if (off[n] != off[0] && !in) return GSV_E_INVALID_ARG;
+    GSVCHK(table_check(in, off, n));
     std::vector<mdx::Header> hdr;
     hdr.reserve(n);
     std::vector<uint64_t> want(n + 1);
     std::vector<uint8_t> st(n);
-    if (!layout(in, off, n, &hdr, want.data(), st.data())) return GSV_E_INVALID_ARG;
+    layout(in, off, n, &hdr, want.data(), st.data());
     // the caller's table is the layout call's for this input
     if (memcmp(want.data(), out_off, (n + 1) * 8) != 0 || (want[n] && !out)) return GSV_E_INVALID_ARG;
     memcpy(status, st.data(), n);
@@ -76,8 +71,7 @@ int gsv_modexp_batch(gsv_ctx* c, const uint8_t* in, const uint64_t* off, size_t 
     for (size_t i = 0; i < n; i++)
         if (mdx::has_work(hdr[i])) group[mdx::width_class((uint32_t)hdr[i].mod_len)].push_back((uint32_t)i);
 
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
+    std::unique_lock<std::mutex> lk(c->mu);
     std::vector<uint8_t> rows, res;
     for (int k = 0; k < mdx::NCLASS; k++) {
         const std::vector<uint32_t>& items = group[k];
@@ -98,14 +92,12 @@ int gsv_modexp_batch(gsv_ctx* c, const uint8_t* in, const uint64_t* off, size_t 
         }
         Layout L;
         const ModexpStage p(L, m * row, m * mw, mdx::work_bytes(m, mw));
-        int rc = arena_reserve(c, L.n);
-        if (rc) return rc;
-        uint8_t *d_in = p.in(c->arena), *d_out = p.out(c->arena), *d_work = p.work(c->arena);
-        HIPCHK(hipMemcpyAsync(d_in, rows.data(), m * row, hipMemcpyHostToDevice, c->stream));
-        rc = gsv_modexp_batch_dev(c, d_in, m, bw, ew, mw, d_out, d_work, c->stream);
-        if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(res.data(), d_out, m * mw, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
+        Staged s(c, L, lk);
+        if (s.rc) return s.rc;
+        GSVCHK(s.in(p.in, rows.data()));
+        GSVCHK(gsv_modexp_batch_dev(c, s(p.in), m, bw, ew, mw, s(p.out), s(p.work), c->stream));
+        GSVCHK(s.out(res.data(), p.out));
+        GSVCHK(s.finish());
         for (size_t j = 0; j < m; j++) {  // the right-aligned modLen bytes of the row
             const uint32_t i = items[j];
             const size_t len = (size_t)hdr[i].mod_len;

@@ -180,7 +180,7 @@ int gsv_notary_synth_dev(gsv_ctx* c, uint64_t seed, uint32_t shard0, size_t n_sh
     if (!c || (n_shards && !d_bodies) || (uint64_t)n_shards * txs_per_shard > 0xFFFFFFFFull) return GSV_E_INVALID_ARG;
     HIPCHK(hipSetDevice(c->device));
     return hip_err(gsv::launch_notary_synth(seed, shard0, (uint32_t)n_shards, txs_per_shard, c->gtab, d_bodies,
-                                            d_exp_status, d_exp_sender, stream ? (hipStream_t)stream : c->stream));
+                                            d_exp_status, d_exp_sender, stream_of(c, stream)));
 }
 
 static int notary_args(const uint8_t* chain_id, size_t chain_id_len, int signer_kind, size_t n_shards,
@@ -223,7 +223,7 @@ int gsv_notary_validate_shards_dev(gsv_ctx* c, const uint8_t* d_bodies, const ui
     Shape* s = shape_find(c, SK_NOTARY, notary_key(h_off, n_shards, chain_id, chain_id_len, signer_kind, max_txs));
     if (!s) return GSV_E_NOT_PREPARED;
     HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     return shape_run(c, *s, st, [&] {
         return notary_run(c, *s, n_shards, d_bodies, d_root32, d_ntx, d_bitmap, d_senders, d_status, st);
     });
@@ -236,41 +236,35 @@ int gsv_notary_validate_shards(gsv_ctx* c, const uint8_t* bodies, const uint64_t
     if (!c || (n_shards && (!bodies || !off || !root32_out || !ntx_out || !valid_bitmap_out))) return GSV_E_INVALID_ARG;
     int rc = notary_args(chain_id, chain_id_len, signer_kind, n_shards, max_txs);
     if (rc || n_shards == 0) return rc;
-    for (size_t i = 0; i < n_shards; i++)
-        if (off[i + 1] < off[i] || off[i + 1] - off[i] > MAX_BODY) return GSV_E_TOO_LARGE;
-    std::lock_guard<std::mutex> g(c->mu);
-    std::lock_guard<std::mutex> g2(c->smu);
-    HIPCHK(hipSetDevice(c->device));
+    GSVCHK(table_check(bodies, off, n_shards, kBodies));
     std::vector<uint64_t> st, en;
     uint64_t pos = stage_offsets(off, n_shards, st, en);
-    size_t bm = (max_txs + 7) / 8, nt = n_shards * (size_t)max_txs;
     Layout staged;
     const NotaryStage p(staged, pos, n_shards, max_txs, senders_out != nullptr, status_out != nullptr);
+    Staged sg(c, staged, Staged::kWithShape);
+    if (sg.rc) return sg.rc;
+    std::lock_guard<std::mutex> g2(c->smu);
     Shape s;
-    rc = shape_temp(c, staged,
-                    [&](Shape& ns, Layout& L) {
-                        return notary_shape(c, ns, st.data(), en.data(), n_shards, chain_id, chain_id_len,
-                                            signer_kind, max_txs, L);
-                    },
-                    s);
-    if (rc) return rc;
-    rc = shape_side_borrow(c, s);
-    if (rc) return rc;
-    uint8_t *d_b = p.bodies(c->arena), *d_r = p.root(c->arena), *d_bm = p.bitmap(c->arena);
-    uint32_t* d_n = p.ntx(c->arena);
-    uint8_t *d_snd = p.senders(c->arena), *d_st = p.status(c->arena);  // nullptr when not asked for
-    rc = stage_bodies(c, d_b, bodies, off, n_shards, st, en);
-    if (rc) return rc;
-    rc = shape_run(c, s, c->stream, [&] {
-        return notary_run(c, s, n_shards, d_b, d_r, d_n, d_bm, d_snd, d_st, c->stream);
-    });
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(root32_out, d_r, n_shards * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(ntx_out, d_n, n_shards * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(valid_bitmap_out, d_bm, n_shards * bm, hipMemcpyDeviceToHost, c->stream));
-    if (senders_out) HIPCHK(hipMemcpyAsync(senders_out, d_snd, nt * 20, hipMemcpyDeviceToHost, c->stream));
-    if (status_out) HIPCHK(hipMemcpyAsync(status_out, d_st, nt, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    GSVCHK(shape_temp(c, staged,
+                      [&](Shape& ns, Layout& L) {
+                          return notary_shape(c, ns, st.data(), en.data(), n_shards, chain_id, chain_id_len,
+                                              signer_kind, max_txs, L);
+                      },
+                      s));
+    GSVCHK(shape_side_borrow(c, s));
+    uint8_t* d_b = sg(p.bodies);
+    GSVCHK(stage_bodies(c, d_b, bodies, off, n_shards, st, en));
+    GSVCHK(shape_run(c, s, c->stream, [&] {
+        // sg(p.senders), sg(p.status): nullptr when not asked for
+        return notary_run(c, s, n_shards, d_b, sg(p.root), sg(p.ntx), sg(p.bitmap), sg(p.senders), sg(p.status),
+                          c->stream);
+    }));
+    GSVCHK(sg.out(root32_out, p.root));
+    GSVCHK(sg.out(ntx_out, p.ntx));
+    GSVCHK(sg.out(valid_bitmap_out, p.bitmap));
+    GSVCHK(sg.out(senders_out, p.senders));
+    GSVCHK(sg.out(status_out, p.status));
+    GSVCHK(sg.finish());
     for (size_t i = 0; i < n_shards; i++)
         if (ntx_out[i] > max_txs) return GSV_E_TOO_LARGE;
     return GSV_SUCCESS;
@@ -364,7 +358,7 @@ int gsv_notary_partition_pack_dev(gsv_ctx* c, const uint8_t* d_bodies, const uin
                           partition_key(h_off, d.n, n_total, nranks, rank, chain_id, chain_id_len, signer_kind, max_txs));
     if (!s) return GSV_E_NOT_PREPARED;
     HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     return shape_run(c, *s, st, [&] { return partition_pack(c, *s, d, d_bodies, d_senders, d_status, d_block, st); });
 }
 
@@ -376,7 +370,7 @@ int gsv_notary_partition_unpack_dev(gsv_ctx* c, const uint8_t* d_blocks, size_t 
     if (n_total > 0xFFFFFFFFull / 4096) return GSV_E_TOO_LARGE;
     PartDims d = part_dims(n_total, nranks, 0, max_txs);
     HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     return hip_err(gsv::launch_partition_unpack(d_blocks, (uint32_t)nranks, (uint32_t)n_total, (uint32_t)d.R,
                                                 (uint32_t)d.bm, d.B, d_root32_all, d_ntx_all, d_bitmap_all,
                                                 d_rank_status, st));
@@ -394,7 +388,7 @@ int gsv_notary_validate_partition_dev(gsv_ctx* c, const uint8_t* d_bodies, const
     if (n_total > 0xFFFFFFFFull / 4096) return GSV_E_TOO_LARGE;
     const int N = c->nranks, r = c->rank;
     PartDims d = part_dims(n_total, N, r, max_txs);
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     // rank-local failures still reach the all-gather with the rank's status in its block header
     int lrc = (!h_off || (d.n && !d_bodies)) ? GSV_E_INVALID_ARG : GSV_SUCCESS;
     bool joined = false;  // this rank has entered the all-gather
@@ -448,20 +442,19 @@ int gsv_notary_validate_partition(gsv_ctx* c, const uint8_t* bodies, const uint6
     if (n_total > 0xFFFFFFFFull / 4096) return GSV_E_TOO_LARGE;
     const int N = c->nranks, r = c->rank;
     PartDims d = part_dims(n_total, N, r, max_txs);
-    const size_t n = d.n, nt = n * (size_t)max_txs;
-    std::lock_guard<std::mutex> g(c->mu);
-    std::lock_guard<std::mutex> g2(c->smu);
-    HIPCHK(hipSetDevice(c->device));
+    const size_t n = d.n;
     hipStream_t sm = c->stream;
     int lrc = (n && !bodies) ? GSV_E_INVALID_ARG : GSV_SUCCESS;
-    for (size_t i = 0; i < n && !lrc; i++)
-        if (off[i + 1] < off[i] || off[i + 1] - off[i] > MAX_BODY) lrc = GSV_E_TOO_LARGE;
+    if (!lrc) lrc = table_check(bodies, off, n, kBodies);
     std::vector<uint64_t> st, en;
     uint64_t pos = n && !lrc ? stage_offsets(off, n, st, en) : 0;
     // gathered outputs + statuses first in the arena (PartitionStage), so a rank whose block failed
     // reserves those alone, finds them at the same place and still joins the collective
     Layout staged;
     const PartitionStage p(staged, d, n_total, N, pos, max_txs, senders_out != nullptr, status_out != nullptr);
+    Staged sg(c, staged, Staged::kWithShape);
+    if (sg.rc) return sg.rc;
+    std::lock_guard<std::mutex> g2(c->smu);
     Shape s;
     if (!lrc) {
         lrc = shape_temp(c, staged,
@@ -474,13 +467,11 @@ int gsv_notary_validate_partition(gsv_ctx* c, const uint8_t* bodies, const uint6
         if (!lrc && n) lrc = shape_side_borrow(c, s);
     }
     if (lrc && arena_reserve(c, p.gathered)) return lrc;  // cannot even join the collective
-    uint8_t *d_blk = p.blk(c->arena), *d_all = p.all(c->arena), *d_oroot = p.oroot(c->arena), *d_obm = p.obm(c->arena);
-    uint32_t* d_ontx = p.ontx(c->arena);
-    int32_t* d_rst = p.rst(c->arena);
-    uint8_t *d_snd = p.own.senders(c->arena), *d_st = p.own.status(c->arena);  // used on success only
+    uint8_t *d_blk = sg(p.blk), *d_all = sg(p.all);
+    uint8_t *d_snd = sg(p.own.senders), *d_st = sg(p.own.status);  // used on success only
     if (!lrc) {
-        uint8_t *d_b = p.own.bodies(c->arena), *d_r = p.own.root(c->arena), *d_bm = p.own.bitmap(c->arena);
-        uint32_t* d_n = p.own.ntx(c->arena);
+        uint8_t *d_b = sg(p.own.bodies), *d_r = sg(p.own.root), *d_bm = sg(p.own.bitmap);
+        uint32_t* d_n = sg(p.own.ntx);
         if (n) lrc = stage_bodies(c, d_b, bodies, off, n, st, en);
         if (!lrc && n)
             lrc = shape_run(c, s, sm, [&] { return notary_run(c, s, n, d_b, d_r, d_n, d_bm, d_snd, d_st, sm); });
@@ -494,15 +485,17 @@ int gsv_notary_validate_partition(gsv_ctx* c, const uint8_t* bodies, const uint6
     int grc = partition_gather(c, d_blk, d_all, d, sm);
     if (grc) return grc;
     HIPCHK(gsv::launch_partition_unpack(d_all, (uint32_t)N, (uint32_t)n_total, (uint32_t)d.R, (uint32_t)d.bm, d.B,
-                                        d_oroot, d_ontx, d_obm, d_rst, sm));
+                                        sg(p.oroot), sg(p.ontx), sg(p.obm), sg(p.rst), sm));
     std::vector<int32_t> rst(N);
-    HIPCHK(hipMemcpyAsync(root32_all, d_oroot, n_total * 32, hipMemcpyDeviceToHost, sm));
-    HIPCHK(hipMemcpyAsync(ntx_all, d_ontx, n_total * 4, hipMemcpyDeviceToHost, sm));
-    HIPCHK(hipMemcpyAsync(bitmap_all, d_obm, n_total * d.bm, hipMemcpyDeviceToHost, sm));
-    HIPCHK(hipMemcpyAsync(rst.data(), d_rst, (size_t)N * 4, hipMemcpyDeviceToHost, sm));
-    if (!lrc && n && senders_out) HIPCHK(hipMemcpyAsync(senders_out, d_snd, nt * 20, hipMemcpyDeviceToHost, sm));
-    if (!lrc && n && status_out) HIPCHK(hipMemcpyAsync(status_out, d_st, nt, hipMemcpyDeviceToHost, sm));
-    HIPCHK(hipStreamSynchronize(sm));
+    GSVCHK(sg.out(root32_all, p.oroot));
+    GSVCHK(sg.out(ntx_all, p.ontx));
+    GSVCHK(sg.out(bitmap_all, p.obm));
+    GSVCHK(sg.out(rst.data(), p.rst));
+    if (!lrc && n) {  // the own block's buffers were reserved and written
+        GSVCHK(sg.out(senders_out, p.own.senders));
+        GSVCHK(sg.out(status_out, p.own.status));
+    }
+    GSVCHK(sg.finish());
     // every rank returns the same verdict: the status of the lowest failing rank
     for (int q = 0; q < N; q++)
         if (rst[q]) return rst[q];

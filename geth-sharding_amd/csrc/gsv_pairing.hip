@@ -201,7 +201,7 @@ extern "C" {
 int gsv_bn256_pairing_prepare(gsv_ctx* c, const uint64_t* h_off, size_t n) {
     if (!c || (n && !h_off)) return GSV_E_INVALID_ARG;
     if (n == 0) return GSV_SUCCESS;
-    if (n > 0xFFFFFFFFull) return GSV_E_TOO_LARGE;
+    if (batch_too_long(n)) return GSV_E_TOO_LARGE;
     std::lock_guard<std::mutex> g(c->smu);
     HIPCHK(hipSetDevice(c->device));
     Shape* s;
@@ -215,41 +215,34 @@ int gsv_bn256_pairing_check_batch_dev(gsv_ctx* c, const uint8_t* d_in, const uin
                                       uint8_t* d_verdict, void* stream) {
     if (!c || (n && (!h_off || !d_verdict))) return GSV_E_INVALID_ARG;
     if (n == 0) return GSV_SUCCESS;
-    if (n > 0xFFFFFFFFull) return GSV_E_TOO_LARGE;
+    if (batch_too_long(n)) return GSV_E_TOO_LARGE;
     std::lock_guard<std::mutex> g(c->smu);
     Shape* s = shape_find(c, SK_PAIRING, pairing_key(h_off, n));
     if (!s) return GSV_E_NOT_PREPARED;
     if (s->pairing.np && !d_in) return GSV_E_INVALID_ARG;
     HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     return shape_run(c, *s, st, [&] { return pairing_run(c, *s, d_in, d_verdict, st); });
 }
 
 int gsv_bn256_pairing_check_batch(gsv_ctx* c, const uint8_t* in, const uint64_t* off, size_t n, uint8_t* verdict) {
     if (!c || (n && (!off || !verdict))) return GSV_E_INVALID_ARG;
     if (n == 0) return GSV_SUCCESS;
-    if (n > 0xFFFFFFFFull) return GSV_E_TOO_LARGE;
-    for (size_t i = 0; i < n; i++)
-        if (off[i + 1] < off[i]) return GSV_E_INVALID_ARG;
-    if (off[n] > off[0] && !in) return GSV_E_INVALID_ARG;
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
-    std::lock_guard<std::mutex> g(c->mu);
-    std::lock_guard<std::mutex> g2(c->smu);
-    HIPCHK(hipSetDevice(c->device));
-    size_t bytes = off[n] - off[0];
+    if (batch_too_long(n)) return GSV_E_TOO_LARGE;
+    GSVCHK(table_check(in, off, n));
+    const std::vector<uint64_t> rel = table_rebase(off, n);
     Layout staged;
-    const PairingStage p(staged, bytes, n);
+    const PairingStage p(staged, off[n] - off[0], n);
+    Staged sg(c, staged, Staged::kWithShape);
+    if (sg.rc) return sg.rc;
+    std::lock_guard<std::mutex> g2(c->smu);
     Shape s;
-    int rc = shape_temp(c, staged, [&](Shape& ns, Layout& L) { return pairing_shape(c, ns, rel.data(), n, L, 1); }, s);
-    if (rc) return rc;
-    uint8_t *d_in = p.in(c->arena), *d_v = p.verdict(c->arena);
-    if (bytes) HIPCHK(hipMemcpyAsync(d_in, in + off[0], bytes, hipMemcpyHostToDevice, c->stream));
-    rc = shape_run(c, s, c->stream, [&] { return pairing_run(c, s, d_in, d_v, c->stream); });
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(verdict, d_v, n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return GSV_SUCCESS;
+    GSVCHK(shape_temp(c, staged, [&](Shape& ns, Layout& L) { return pairing_shape(c, ns, rel.data(), n, L, 1); }, s));
+    uint8_t *d_in = sg(p.in), *d_v = sg(p.verdict);
+    GSVCHK(sg.in(p.in, in + off[0], off[n] - off[0]));
+    GSVCHK(shape_run(c, s, c->stream, [&] { return pairing_run(c, s, d_in, d_v, c->stream); }));
+    GSVCHK(sg.out(verdict, p.verdict));
+    return sg.finish();
 }
 
 int gsv_bn256_synth_checks_dev(gsv_ctx* c, uint64_t seed, size_t nchecks, uint8_t* d_out768, uint8_t* d_expect,
@@ -257,7 +250,7 @@ int gsv_bn256_synth_checks_dev(gsv_ctx* c, uint64_t seed, size_t nchecks, uint8_
     if (!c || (nchecks && !d_out768) || nchecks > 0x3FFFFFFFull) return GSV_E_INVALID_ARG;
     HIPCHK(hipSetDevice(c->device));
     return hip_err(gsv::launch_bn256_synth(seed, (uint32_t)nchecks, d_out768, d_expect,
-                                           stream ? (hipStream_t)stream : c->stream));
+                                           stream_of(c, stream)));
 }
 
 }  // extern "C"

@@ -220,7 +220,7 @@ int gsv_blob_serialize_batch_dev(gsv_ctx* c, const uint8_t* d_blobs, const uint6
     if (!s) return GSV_E_NOT_PREPARED;
     if (s->ser.nchunks && (!d_blobs || !d_bodies_out || misaligned16(d_bodies_out))) return GSV_E_INVALID_ARG;
     HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     return shape_run(c, *s, st, [&] { return ser_run(*s, d_blobs, d_skip_evm, d_bodies_out, st); });
 }
 
@@ -239,40 +239,34 @@ int gsv_blob_serialize_batch(gsv_ctx* c, const uint8_t* blobs, const uint64_t* b
     const uint64_t b0 = blob_off[list_off[0]], nbytes = blob_off[list_off[n_lists]] - b0;
     const uint64_t k0 = list_off[0], nblobs = list_off[n_lists] - k0;
     std::vector<uint64_t> rb = rebase(blob_off, list_off, n_lists);
-    std::lock_guard<std::mutex> g(c->mu);
-    std::lock_guard<std::mutex> g2(c->smu);
-    HIPCHK(hipSetDevice(c->device));
     Layout staged;
     const BlobSerStage p(staged, nbytes, nblobs, skip_evm != nullptr, total);
+    Staged sg(c, staged, Staged::kWithShape);
+    if (sg.rc) return sg.rc;
+    std::lock_guard<std::mutex> g2(c->smu);
     Shape s;
     std::vector<uint64_t> body_off;
-    rc = shape_temp(c, staged,
-                    [&](Shape& ns, Layout& L) {
-                        ns.kind = SK_BLOB_SER;
-                        return ser_shape(ns, rb.data(), list_off, n_lists, false, L, body_off);
-                    },
-                    s);
-    if (rc) return rc;
-    uint8_t *d_b = p.blobs(c->arena), *d_sk = p.skip(c->arena), *d_o = p.bodies(c->arena);
-    HIPCHK(hipMemcpyAsync(d_b, blobs + b0, nbytes, hipMemcpyHostToDevice, c->stream));
-    if (d_sk) HIPCHK(hipMemcpyAsync(d_sk, skip_evm + k0, nblobs, hipMemcpyHostToDevice, c->stream));
+    GSVCHK(shape_temp(c, staged,
+                      [&](Shape& ns, Layout& L) {
+                          ns.kind = SK_BLOB_SER;
+                          return ser_shape(ns, rb.data(), list_off, n_lists, false, L, body_off);
+                      },
+                      s));
+    uint8_t *d_b = sg(p.blobs), *d_sk = sg(p.skip), *d_o = sg(p.bodies);
+    GSVCHK(sg.in(p.blobs, blobs + b0));
+    if (skip_evm) GSVCHK(sg.in(p.skip, skip_evm + k0));
     // the plan numbers blobs from list_off[0]; the staged flags start there too
-    rc = shape_run(c, s, c->stream, [&] { return ser_run(s, d_b, d_sk ? d_sk - k0 : nullptr, d_o, c->stream); });
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(bodies_out, d_o, total, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return GSV_SUCCESS;
+    GSVCHK(shape_run(c, s, c->stream, [&] { return ser_run(s, d_b, d_sk ? d_sk - k0 : nullptr, d_o, c->stream); }));
+    GSVCHK(sg.out(bodies_out, p.bodies));
+    return sg.finish();
 }
 
 // ------------------------------------------------------------------ utils.Deserialize
 int gsv_blob_data_layout(const uint64_t* off, size_t n, uint64_t* data_off_out) {
     if (!data_off_out || (n && !off)) return GSV_E_INVALID_ARG;
     data_off_out[0] = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (off[i + 1] < off[i]) return GSV_E_INVALID_ARG;
-        if (off[i + 1] - off[i] > MAX_BODY) return GSV_E_TOO_LARGE;
-        data_off_out[i + 1] = data_off_out[i] + data_region(off[i + 1] - off[i]);
-    }
+    GSVCHK(table_order(off, n, kBlobBodies));
+    for (size_t i = 0; i < n; i++) data_off_out[i + 1] = data_off_out[i] + data_region(off[i + 1] - off[i]);
     return GSV_SUCCESS;
 }
 
@@ -299,7 +293,7 @@ int gsv_blob_deserialize_batch_dev(gsv_ctx* c, const uint8_t* d_bodies, const ui
     Shape* s = shape_find(c, SK_BLOB_DESER, deser_key(h_off, n, max_blobs));
     if (!s) return GSV_E_NOT_PREPARED;
     HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     return shape_run(c, *s, st, [&] {
         return deser_run(*s, n, max_blobs, d_bodies, d_nblobs, d_blob_start, d_blob_len, d_skip_evm, d_data, st);
     });
@@ -311,46 +305,40 @@ int gsv_blob_deserialize_batch(gsv_ctx* c, const uint8_t* bodies, const uint64_t
     blob_off_out[0] = 0;
     if (n == 0) return GSV_SUCCESS;
     if (n > MAX_LISTS) return GSV_E_INVALID_ARG;
+    GSVCHK(table_order(off, n, kBlobBodies));
     uint64_t most = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (off[i + 1] < off[i]) return GSV_E_INVALID_ARG;
-        if (off[i + 1] - off[i] > MAX_BODY) return GSV_E_TOO_LARGE;
-        most = std::max(most, (off[i + 1] - off[i]) / CHUNK);
-    }
+    for (size_t i = 0; i < n; i++) most = std::max(most, (off[i + 1] - off[i]) / CHUNK);
     if (most == 0) {  // no whole chunk anywhere: no blobs
         for (size_t i = 0; i < n; i++) nblobs_out[i] = 0;
         return GSV_SUCCESS;
     }
     if (!bodies || !skip_evm_out || !data_out) return GSV_E_INVALID_ARG;
     const uint32_t max_blobs = (uint32_t)most;  // every blob takes a chunk: nothing is cut off
-    std::lock_guard<std::mutex> g(c->mu);
-    std::lock_guard<std::mutex> g2(c->smu);
-    HIPCHK(hipSetDevice(c->device));
     std::vector<uint64_t> st, en, doff(n + 1, 0);
     const uint64_t pos = stage_offsets(off, n, st, en);
     for (size_t i = 0; i < n; i++) doff[i + 1] = doff[i] + data_region(off[i + 1] - off[i]);
     Layout staged;
     const BlobDeserStage p(staged, pos + 16, n, max_blobs, doff[n]);
+    Staged sg(c, staged, Staged::kWithShape);
+    if (sg.rc) return sg.rc;
+    std::lock_guard<std::mutex> g2(c->smu);
     Shape s;
-    int rc = shape_temp(c, staged,
-                        [&](Shape& ns, Layout& L) { return deser_shape(ns, st.data(), en.data(), n, max_blobs, L); }, s);
-    if (rc) return rc;
-    uint8_t *d_b = p.bodies(c->arena), *d_sk = p.skip(c->arena), *d_d = p.data(c->arena);
-    uint32_t *d_n = p.nblobs(c->arena), *d_s = p.start(c->arena), *d_l = p.len(c->arena);
-    rc = stage_bodies(c, d_b, bodies, off, n, st, en);
-    if (rc) return rc;
-    rc = shape_run(c, s, c->stream,
-                   [&] { return deser_run(s, n, max_blobs, d_b, d_n, d_s, d_l, d_sk, d_d, c->stream); });
-    if (rc) return rc;
+    GSVCHK(shape_temp(c, staged,
+                      [&](Shape& ns, Layout& L) { return deser_shape(ns, st.data(), en.data(), n, max_blobs, L); }, s));
+    uint8_t *d_b = sg(p.bodies), *d_sk = sg(p.skip), *d_d = sg(p.data);
+    uint32_t *d_n = sg(p.nblobs), *d_s = sg(p.start), *d_l = sg(p.len);
+    GSVCHK(stage_bodies(c, d_b, bodies, off, n, st, en));
+    GSVCHK(shape_run(c, s, c->stream,
+                     [&] { return deser_run(s, n, max_blobs, d_b, d_n, d_s, d_l, d_sk, d_d, c->stream); }));
     const size_t rows = n * (size_t)max_blobs;
     std::vector<uint32_t> hs(rows), hl(rows);
     std::vector<uint8_t> hk(rows), hd(doff[n]);
-    HIPCHK(hipMemcpyAsync(nblobs_out, d_n, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(hs.data(), d_s, rows * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(hl.data(), d_l, rows * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(hk.data(), d_sk, rows, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(hd.data(), d_d, doff[n], hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    GSVCHK(sg.out(nblobs_out, p.nblobs));
+    GSVCHK(sg.out(hs.data(), p.start));
+    GSVCHK(sg.out(hl.data(), p.len));
+    GSVCHK(sg.out(hk.data(), p.skip));
+    GSVCHK(sg.out(hd.data(), p.data));
+    GSVCHK(sg.finish());
     // compact into the reference's list of byte strings: the filler between blobs drops out here
     uint64_t k = 0, w = 0;
     for (size_t i = 0; i < n; i++)
@@ -407,7 +395,7 @@ int gsv_proposer_create_collations_dev(gsv_ctx* c, const uint8_t* d_blobs, const
     if (!s) return GSV_E_NOT_PREPARED;
     if (s->ser.nchunks && (!d_blobs || !d_bodies_out || misaligned16(d_bodies_out))) return GSV_E_INVALID_ARG;
     HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     return shape_run(c, *s, st, [&] {
         return proposer_run(c, *s, n, d_blobs, d_shard_id32, d_period32, d_proposer20, d_seckey32, d_bodies_out,
                             d_chunk_root32, d_hash32, d_sig65, d_status, st);
@@ -433,36 +421,32 @@ int gsv_proposer_create_collations(gsv_ctx* c, const uint8_t* blobs, const uint6
     if (total && (!blobs || !bodies_out)) return GSV_E_INVALID_ARG;
     const uint64_t b0 = blob_off[list_off[0]], nbytes = blob_off[list_off[n]] - b0;
     std::vector<uint64_t> rb = rebase(blob_off, list_off, n);
-    std::lock_guard<std::mutex> g(c->mu);
-    std::lock_guard<std::mutex> g2(c->smu);
-    HIPCHK(hipSetDevice(c->device));
     Layout staged;
     const ProposerStage p(staged, n, nbytes, total);
+    Staged sg(c, staged, Staged::kWithShape);
+    if (sg.rc) return sg.rc;
+    std::lock_guard<std::mutex> g2(c->smu);
     Shape s;
     std::vector<uint64_t> body_off;
-    rc = shape_temp(c, staged,
-                    [&](Shape& ns, Layout& L) { return proposer_shape(c, ns, rb.data(), list_off, n, L, body_off); }, s);
-    if (rc) return rc;
-    uint8_t* a = c->arena;
-    uint8_t *d_key = p.key(a), *d_b = p.blobs(a), *d_sid = p.sid(a), *d_per = p.per(a), *d_prop = p.prop(a);
-    uint8_t *d_o = p.bodies(a), *d_root = p.root(a), *d_hash = p.hash(a), *d_sig = p.sig(a), *d_st = p.st(a);
+    GSVCHK(shape_temp(c, staged,
+                      [&](Shape& ns, Layout& L) { return proposer_shape(c, ns, rb.data(), list_off, n, L, body_off); }, s));
     hipStream_t st = c->stream;
-    SecretWipe wipe{c, d_key, n * 32};  // from here on the keys may be in HBM
-    HIPCHK(hipMemcpyAsync(d_key, seckey32, n * 32, hipMemcpyHostToDevice, st));
-    if (nbytes && blobs) HIPCHK(hipMemcpyAsync(d_b, blobs + b0, nbytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_sid, shard_id32, n * 32, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_per, period32, n * 32, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_prop, proposer20, n * 20, hipMemcpyHostToDevice, st));
-    rc = shape_run(c, s, st, [&] {
-        return proposer_run(c, s, n, d_b, d_sid, d_per, d_prop, d_key, d_o, d_root, d_hash, d_sig, d_st, st);
-    });
-    if (rc) return rc;
-    if (total) HIPCHK(hipMemcpyAsync(bodies_out, d_o, total, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(chunk_root32_out, d_root, n * 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(hash32_out, d_hash, n * 32, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(sig65_out, d_sig, n * 65, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, st));
-    return wipe.finish();
+    sg.secret(p.key);  // from here on the keys may be in HBM
+    GSVCHK(sg.in(p.key, seckey32));
+    if (blobs) GSVCHK(sg.in(p.blobs, blobs + b0));
+    GSVCHK(sg.in(p.sid, shard_id32));
+    GSVCHK(sg.in(p.per, period32));
+    GSVCHK(sg.in(p.prop, proposer20));
+    GSVCHK(shape_run(c, s, st, [&] {
+        return proposer_run(c, s, n, sg(p.blobs), sg(p.sid), sg(p.per), sg(p.prop), sg(p.key), sg(p.bodies), sg(p.root),
+                            sg(p.hash), sg(p.sig), sg(p.st), st);
+    }));
+    GSVCHK(sg.out(bodies_out, p.bodies));
+    GSVCHK(sg.out(chunk_root32_out, p.root));
+    GSVCHK(sg.out(hash32_out, p.hash));
+    GSVCHK(sg.out(sig65_out, p.sig));
+    GSVCHK(sg.out(status, p.st));
+    return sg.finish();
 }
 
 }  // extern "C"

@@ -101,7 +101,6 @@ int stage_bodies(gsv_ctx* c, uint8_t* d_b, const uint8_t* bodies, const uint64_t
 
 namespace {
 
-constexpr uint64_t MAX_POC = 1ull << 26;   // salted bodies (Proof of Custody)
 constexpr uint64_t MAX_LIST = 1ull << 24;  // generic DeriveSha items per list
 
 // ---- chunk root: key = body offsets
@@ -254,43 +253,34 @@ int gsv_chunk_root_batch_dev(gsv_ctx* c, const uint8_t* d_bodies, const uint64_t
     Shape* s = shape_find(c, SK_CHUNK, chunk_key(h_off, n));
     if (!s) return GSV_E_NOT_PREPARED;
     HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     return shape_run(c, *s, st, [&] { return chunk_run(c, *s, s->chunk, d_bodies, d_root32_out, st); });
 }
 
 int gsv_chunk_root_batch(gsv_ctx* c, const uint8_t* bodies, const uint64_t* off, size_t n, uint8_t* root32_out) {
     if (!c || (n && (!off || !root32_out))) return GSV_E_INVALID_ARG;
     if (n == 0) return GSV_SUCCESS;
-    for (size_t i = 0; i < n; i++)
-        if (off[i + 1] < off[i] || off[i + 1] - off[i] > MAX_BODY) return GSV_E_TOO_LARGE;
-    if (off[n] > off[0] && !bodies) return GSV_E_INVALID_ARG;
-    std::lock_guard<std::mutex> g(c->mu);
-    std::lock_guard<std::mutex> g2(c->smu);
-    HIPCHK(hipSetDevice(c->device));
+    GSVCHK(table_check(bodies, off, n, kBodies));
     std::vector<uint64_t> st, en;
     uint64_t pos = stage_offsets(off, n, st, en);
     Layout staged;
     const RootsStage p(staged, pos, n);
+    Staged sg(c, staged, Staged::kWithShape);
+    if (sg.rc) return sg.rc;
+    std::lock_guard<std::mutex> g2(c->smu);
     Shape s;
-    int rc = shape_temp(c, staged, [&](Shape& ns, Layout& L) { return chunk_shape(c, ns, st.data(), en.data(), n, L); },
-                        s);
-    if (rc) return rc;
-    uint8_t *d_b = p.in(c->arena), *d_r = p.roots(c->arena);
-    rc = stage_bodies(c, d_b, bodies, off, n, st, en);
-    if (rc) return rc;
-    rc = shape_run(c, s, c->stream, [&] { return chunk_run(c, s, s.chunk, d_b, d_r, c->stream); });
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(root32_out, d_r, n * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return GSV_SUCCESS;
+    GSVCHK(shape_temp(c, staged, [&](Shape& ns, Layout& L) { return chunk_shape(c, ns, st.data(), en.data(), n, L); },
+                      s));
+    uint8_t *d_b = sg(p.in), *d_r = sg(p.roots);
+    GSVCHK(stage_bodies(c, d_b, bodies, off, n, st, en));
+    GSVCHK(shape_run(c, s, c->stream, [&] { return chunk_run(c, s, s.chunk, d_b, d_r, c->stream); }));
+    GSVCHK(sg.out(root32_out, p.roots));
+    return sg.finish();
 }
 
 // ------------------------------------------------------------------ DeriveSha over any DerivableList
 static int derive_args(const uint64_t* voff, const uint64_t* list_off, size_t n) {
-    if (list_off[n] < list_off[0]) return GSV_E_INVALID_ARG;
-    for (size_t i = 0; i < n; i++)
-        if (list_off[i + 1] < list_off[i]) return GSV_E_INVALID_ARG;
-    return GSV_SUCCESS;
+    return table_order(list_off, n);  // the lists' table; derive_shape checks the values' table it indexes
 }
 
 int gsv_derive_sha_prepare(gsv_ctx* c, const uint64_t* voff, const uint64_t* list_off, size_t n) {
@@ -316,7 +306,7 @@ int gsv_derive_sha_batch_dev(gsv_ctx* c, const uint8_t* d_vals, const uint64_t* 
     Shape* s = shape_find(c, SK_DERIVE, derive_key(voff, list_off, n));
     if (!s) return GSV_E_NOT_PREPARED;
     HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     return shape_run(c, *s, st, [&] { return derive_run(c, *s, d_vals, d_root32_out, st); });
 }
 
@@ -328,25 +318,22 @@ int gsv_derive_sha_batch(gsv_ctx* c, const uint8_t* vals, const uint64_t* voff, 
     if (rc) return rc;
     uint64_t v0 = voff[list_off[0]], v1 = voff[list_off[n]];
     if (v1 < v0 || (v1 > v0 && !vals)) return GSV_E_INVALID_ARG;
-    std::lock_guard<std::mutex> g(c->mu);
-    std::lock_guard<std::mutex> g2(c->smu);
-    HIPCHK(hipSetDevice(c->device));
     // stage the values (rebased so item list_off[0] starts at 0)
     std::vector<uint64_t> rv(list_off[n] + 1, 0);
     for (uint64_t k = list_off[0]; k <= list_off[n]; k++) rv[k] = voff[k] - v0;
     Layout staged;
     const RootsStage p(staged, v1 - v0, n);
+    Staged sg(c, staged, Staged::kWithShape);
+    if (sg.rc) return sg.rc;
+    std::lock_guard<std::mutex> g2(c->smu);
     Shape s;
-    rc = shape_temp(c, staged, [&](Shape& ns, Layout& L) { return derive_shape(c, ns, rv.data(), list_off, n, L); },
-                    s);
-    if (rc) return rc;
-    uint8_t *d_v = p.in(c->arena), *d_r = p.roots(c->arena);
-    if (v1 > v0) HIPCHK(hipMemcpyAsync(d_v, vals + v0, v1 - v0, hipMemcpyHostToDevice, c->stream));
-    rc = shape_run(c, s, c->stream, [&] { return derive_run(c, s, d_v, d_r, c->stream); });
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(root32_out, d_r, n * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return GSV_SUCCESS;
+    GSVCHK(shape_temp(c, staged, [&](Shape& ns, Layout& L) { return derive_shape(c, ns, rv.data(), list_off, n, L); },
+                      s));
+    uint8_t *d_v = sg(p.in), *d_r = sg(p.roots);
+    GSVCHK(sg.in(p.in, vals + v0, v1 - v0));
+    GSVCHK(shape_run(c, s, c->stream, [&] { return derive_run(c, s, d_v, d_r, c->stream); }));
+    GSVCHK(sg.out(root32_out, p.roots));
+    return sg.finish();
 }
 
 // ------------------------------------------------------------------ Proof of Custody
@@ -369,7 +356,7 @@ int gsv_collation_poc_batch_dev(gsv_ctx* c, const uint8_t* d_bodies, const uint6
     Shape* s = shape_find(c, SK_POC, poc_key(h_off, n, salt, salt_len));
     if (!s) return GSV_E_NOT_PREPARED;
     HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     return shape_run(c, *s, st, [&] { return poc_run(c, *s, n, d_bodies, d_poc32_out, st); });
 }
 
@@ -377,31 +364,23 @@ int gsv_collation_poc_batch(gsv_ctx* c, const uint8_t* bodies, const uint64_t* o
                             size_t salt_len, uint8_t* poc32_out) {
     if (!c || (n && (!off || !poc32_out)) || (salt_len && !salt)) return GSV_E_INVALID_ARG;
     if (n == 0) return GSV_SUCCESS;
-    for (size_t i = 0; i < n; i++)
-        if (off[i + 1] < off[i] || off[i + 1] - off[i] > MAX_POC) return GSV_E_TOO_LARGE;
-    if (off[n] > off[0] && !bodies) return GSV_E_INVALID_ARG;
-    std::lock_guard<std::mutex> g(c->mu);
-    std::lock_guard<std::mutex> g2(c->smu);
-    HIPCHK(hipSetDevice(c->device));
+    GSVCHK(table_check(bodies, off, n, kPocBodies));
     std::vector<uint64_t> st, en;
     uint64_t pos = stage_offsets(off, n, st, en);
     Layout staged;
     const RootsStage p(staged, pos, n);
+    Staged sg(c, staged, Staged::kWithShape);
+    if (sg.rc) return sg.rc;
+    std::lock_guard<std::mutex> g2(c->smu);
     Shape s;
-    int rc = shape_temp(c, staged,
-                        [&](Shape& ns, Layout& L) {
-                            return poc_shape(c, ns, st.data(), en.data(), n, salt, salt_len, L);
-                        },
-                        s);
-    if (rc) return rc;
-    uint8_t *d_b = p.in(c->arena), *d_r = p.roots(c->arena);
-    rc = stage_bodies(c, d_b, bodies, off, n, st, en);
-    if (rc) return rc;
-    rc = shape_run(c, s, c->stream, [&] { return poc_run(c, s, n, d_b, d_r, c->stream); });
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(poc32_out, d_r, n * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return GSV_SUCCESS;
+    GSVCHK(shape_temp(c, staged,
+                      [&](Shape& ns, Layout& L) { return poc_shape(c, ns, st.data(), en.data(), n, salt, salt_len, L); },
+                      s));
+    uint8_t *d_b = sg(p.in), *d_r = sg(p.roots);
+    GSVCHK(stage_bodies(c, d_b, bodies, off, n, st, en));
+    GSVCHK(shape_run(c, s, c->stream, [&] { return poc_run(c, s, n, d_b, d_r, c->stream); }));
+    GSVCHK(sg.out(poc32_out, p.roots));
+    return sg.finish();
 }
 
 // ------------------------------------------------------------------ collation header + proposer signature
@@ -427,7 +406,7 @@ int gsv_collation_header_verify_batch_dev(gsv_ctx* c, const uint8_t* d_sid, cons
     Shape* s = shape_find(c, SK_HEADER, std::vector<uint64_t>{n});
     if (!s) return GSV_E_NOT_PREPARED;
     HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     return shape_run(c, *s, st, [&] {
         KTimer t(c, GSV_K_HEADER, st);
         return hip_err(gsv::launch_header_verify(d_sid, d_root, d_per, d_prop, d_sig, d_nil, (uint32_t)n, c->gtab,
@@ -443,34 +422,27 @@ int gsv_collation_header_verify_batch(gsv_ctx* c, const uint8_t* shard_id32, con
         return GSV_E_INVALID_ARG;
     if (n == 0) return GSV_SUCCESS;
     if (n > (1u << 30)) return GSV_E_TOO_LARGE;
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
     Layout L;
     const HeaderStage p(L, n, gsv::header_scratch_bytes((uint32_t)n), nil_flags != nullptr, hash32_out != nullptr,
                         signer20_out != nullptr);
-    int rc = arena_reserve(c, L.n);
-    if (rc) return rc;
-    uint8_t *d_sid = p.sid(c->arena), *d_root = p.root(c->arena), *d_per = p.per(c->arena);
-    uint8_t *d_prop = p.prop(c->arena), *d_sig = p.sig(c->arena);
-    uint8_t *d_nil = p.nil(c->arena), *d_hash = p.hash(c->arena), *d_signer = p.signer(c->arena);  // or nullptr
-    uint8_t *d_st = p.st(c->arena), *d_scr = p.scr(c->arena);
-    hipStream_t st = c->stream;
-    HIPCHK(hipMemcpyAsync(d_sid, shard_id32, n * 32, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_root, chunk_root32, n * 32, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_per, period32, n * 32, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_prop, proposer20, n * 20, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_sig, sig65, n * 65, hipMemcpyHostToDevice, st));
-    if (d_nil) HIPCHK(hipMemcpyAsync(d_nil, nil_flags, n, hipMemcpyHostToDevice, st));
+    Staged s(c, L);
+    if (s.rc) return s.rc;
+    GSVCHK(s.in(p.sid, shard_id32));
+    GSVCHK(s.in(p.root, chunk_root32));
+    GSVCHK(s.in(p.per, period32));
+    GSVCHK(s.in(p.prop, proposer20));
+    GSVCHK(s.in(p.sig, sig65));
+    GSVCHK(s.in(p.nil, nil_flags));
     {
-        KTimer t(c, GSV_K_HEADER, st);
-        HIPCHK(gsv::launch_header_verify(d_sid, d_root, d_per, d_prop, d_sig, d_nil, (uint32_t)n, c->gtab, d_scr,
-                                         d_hash, d_signer, d_st, st));
+        // s(p.nil), s(p.hash), s(p.signer): nullptr when absent
+        KTimer t(c, GSV_K_HEADER, c->stream);
+        HIPCHK(gsv::launch_header_verify(s(p.sid), s(p.root), s(p.per), s(p.prop), s(p.sig), s(p.nil), (uint32_t)n,
+                                         c->gtab, s(p.scr), s(p.hash), s(p.signer), s(p.st), c->stream));
     }
-    if (hash32_out) HIPCHK(hipMemcpyAsync(hash32_out, d_hash, n * 32, hipMemcpyDeviceToHost, st));
-    if (signer20_out) HIPCHK(hipMemcpyAsync(signer20_out, d_signer, n * 20, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return GSV_SUCCESS;
+    GSVCHK(s.out(hash32_out, p.hash));
+    GSVCHK(s.out(signer20_out, p.signer));
+    GSVCHK(s.out(status, p.st));
+    return s.finish();
 }
 
 }  // extern "C"

@@ -29,7 +29,7 @@ int gsv_tx_sign_batch_dev(gsv_ctx* c, const uint8_t* d_rlp, const uint64_t* d_of
                           uint32_t* d_out_len, uint8_t* d_txhash32_out, uint8_t* d_status, uint8_t* d_work,
                           void* stream) {
     if (!signer_args_ok(c, chain_id, chain_id_len, signer_kind)) return GSV_E_INVALID_ARG;
-    if ((n && (!d_rlp || !d_off || !d_seckey32 || !d_out || !d_out_len || !d_status || !d_work)) || n > 0xFFFFFFFFull ||
+    if ((n && (!d_rlp || !d_off || !d_seckey32 || !d_out || !d_out_len || !d_status || !d_work)) || batch_too_long(n) ||
         ((uintptr_t)d_work & 15) || ((uintptr_t)d_out_len & 3) || ((uintptr_t)d_txhash32_out & 3))
         return GSV_E_INVALID_ARG;
     if (n == 0) return GSV_SUCCESS;
@@ -45,7 +45,7 @@ int gsv_tx_sign_batch_dev(gsv_ctx* c, const uint8_t* d_rlp, const uint64_t* d_of
             pack_words(vt.w + r * gsv::TXS_V_WORDS, 0, b, vt.len[r]);
         }
     }
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    hipStream_t st = stream_of(c, stream);
     uint32_t* rec = (uint32_t*)d_work;
     uint8_t *msg = d_work + n * 16, *sig = d_work + n * 48, *sst = d_work + n * 113;
     {
@@ -65,38 +65,28 @@ int gsv_tx_sign_batch(gsv_ctx* c, const uint8_t* rlp, const uint64_t* off, size_
                       const uint8_t* chain_id, size_t chain_id_len, int signer_kind, uint8_t* out, uint32_t* out_len,
                       uint8_t* txhash32_out, uint8_t* status) {
     if (!signer_args_ok(c, chain_id, chain_id_len, signer_kind)) return GSV_E_INVALID_ARG;
-    if ((n && (!off || !seckey32 || !out || !out_len || !status)) || n > 0xFFFFFFFFull) return GSV_E_INVALID_ARG;
+    if ((n && (!off || !seckey32 || !out || !out_len || !status)) || batch_too_long(n)) return GSV_E_INVALID_ARG;
     if (n == 0) return GSV_SUCCESS;
-    for (size_t i = 0; i < n; i++)  // the kernels trust off[i] <= off[i+1]
-        if (off[i + 1] < off[i]) return GSV_E_INVALID_ARG;
+    GSVCHK(table_check(rlp, off, n));  // the kernels trust off[i] <= off[i+1]
     const size_t bytes = off[n] - off[0], G = GSV_TX_SIGN_GROWTH(chain_id_len);
-    if (bytes && !rlp) return GSV_E_INVALID_ARG;
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
+    const std::vector<uint64_t> rel = table_rebase(off, n);
     std::vector<uint8_t> slots(bytes + n * G);  // the staged slots; only each item's own bytes reach `out`
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->device));
     Layout L;
     const TxSignStage p(L, n, gsv::TXS_WORK_PER, bytes, G, txhash32_out != nullptr);
-    int rc = arena_reserve(c, L.n);
-    if (rc) return rc;
-    uint8_t *d_key = p.key(c->arena), *d_work = p.work(c->arena), *d_rlp = p.rlp(c->arena), *d_out = p.out(c->arena);
-    uint8_t *d_hash = p.hash(c->arena), *d_st = p.st(c->arena);  // d_hash: nullptr when not asked for
-    uint64_t* d_off = p.off(c->arena);
-    uint32_t* d_olen = p.olen(c->arena);
-    SecretWipe wipe{c, d_key, n * 32};  // from here on the keys may be in HBM
-    HIPCHK(hipMemcpyAsync(d_key, seckey32, n * 32, hipMemcpyHostToDevice, c->stream));
-    if (bytes) HIPCHK(hipMemcpyAsync(d_rlp, rlp + off[0], bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_off, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    rc = gsv_tx_sign_batch_dev(c, d_rlp, d_off, n, d_key, chain_id, chain_id_len, signer_kind, d_out, d_olen, d_hash,
-                               d_st, d_work, c->stream);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(slots.data(), d_out, slots.size(), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(out_len, d_olen, n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (txhash32_out) HIPCHK(hipMemcpyAsync(txhash32_out, d_hash, n * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, c->stream));
-    rc = wipe.finish();
-    if (rc) return rc;
+    Staged s(c, L);
+    if (s.rc) return s.rc;
+    s.secret(p.key);  // from here on the keys may be in HBM
+    GSVCHK(s.in(p.key, seckey32));
+    GSVCHK(s.in(p.rlp, rlp + off[0], bytes));
+    GSVCHK(s.in(p.off, rel.data()));
+    // s(p.hash): nullptr when not asked for
+    GSVCHK(gsv_tx_sign_batch_dev(c, s(p.rlp), s(p.off), n, s(p.key), chain_id, chain_id_len, signer_kind, s(p.out),
+                                 s(p.olen), s(p.hash), s(p.st), s(p.work), c->stream));
+    GSVCHK(s.out(slots.data(), p.out));
+    GSVCHK(s.out(out_len, p.olen));
+    GSVCHK(s.out(txhash32_out, p.hash));
+    GSVCHK(s.out(status, p.st));
+    GSVCHK(s.finish());
     for (size_t i = 0; i < n; i++) {
         const size_t slot = rel[i] + i * G;
         // a length past the slot cannot come from the kernel; it is not trusted with the caller's memory

@@ -2,8 +2,10 @@
 // compiles it with g++).  A Layout collects 256-B aligned regions first and is bound to memory
 // afterwards: a prepared shape's workspace (Shape::at) and the buffers a host-pointer entry point
 // stages in the context's arena.  Every staged buffer is declared once, in the *Stage struct of its
-// entry point; the total to reserve is the Layout's `n` after those declarations, and a pointer exists
-// only once the arena is reserved (arena_reserve may move it): buf(c->arena).
+// entry point; the total to reserve is the Layout's `n` after those declarations.  A pointer exists only once
+// the arena is reserved, and is bound after the call's last reservation (arena_reserve may move the arena):
+// the host forms bind through their Staged (gsv_ctx.h), s(buf), which also copies no more into or out of a
+// buffer than the `bytes` declared here.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -286,6 +288,12 @@ struct BlockHeaderStage {
           nonce(L.buf<uint64_t>(n * 8, rules)), number(L.buf<uint64_t>(n * 8, rules)),
           time(L.buf<uint64_t>(n * 8, calc)), mix(L.buf(n * 32, rules)), diff(L.buf(n * 32, rules)),
           want(L.buf(n * 32, rules || calc)), pre(L.buf(n)), post(L.buf(n, rules)) {}
+};
+// the last step of gsv_ethash_verify_headers_batch, staged again behind the ethash path's own use of the
+// arena: the three statuses of each header in, the merged one out
+struct BlockMergeStage {
+    B8 pre, seal, post, out;
+    BlockMergeStage(Layout& L, size_t n) : pre(L.buf(n)), seal(L.buf(n)), post(L.buf(n)), out(L.buf(n)) {}
 };
 
 }  // namespace api

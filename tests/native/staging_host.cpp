@@ -150,6 +150,17 @@ int main() {
                        reg("sig", p.sig), reg("nil", p.nil, opt), reg("hash", p.hash, opt),
                        reg("signer", p.signer, opt), reg("st", p.st), reg("scr", p.scr)});
             }
+            {
+                Layout L;
+                BlockMergeStage p(L, n);
+                check("ethash_verify_headers_batch (merge)" + tag, L,
+                      {reg("pre", p.pre), reg("seal", p.seal), reg("post", p.post), reg("out", p.out)});
+                for (const B8* b : {&p.pre, &p.seal, &p.post, &p.out})  // a status byte per header, each way
+                    if (b->bytes != n) {
+                        printf("FAIL merge stage%s: a buffer of %zu bytes for %zu headers\n", tag.c_str(), b->bytes, n);
+                        g_fail++;
+                    }
+            }
         }
     // the partition with an empty local block (n = 0, n_total = 3, 2 ranks): part_dims leaves a rank
     // without shards only when n_total < ranks, so the block is emptied by hand here, and the real case

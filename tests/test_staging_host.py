@@ -1,7 +1,8 @@
 """CPU check of the staging plans of the 14 host-pointer entry points (csrc/staging.h: one declaration
 per staged device buffer, the total to reserve derived from those declarations): tests/native/
 staging_host.cpp rebuilds each plan with the structs the entry points use, for n in {1, 3}, with every
-optional output absent and present, and the partition path with an empty local block, and checks that
+optional output absent and present, the partition path with an empty local block, and the merge stage at
+the end of gsv_ethash_verify_headers_batch (a status byte per header in each buffer), and checks that
 every offset is 256-aligned, the buffers are pairwise disjoint, the last ends at or before the total,
 and the temporary shape's offset is that total.  A stand-alone program (g++, with ASan + UBSan when
 the compiler links them), run as a child process."""
