@@ -7,6 +7,7 @@
 //   gsv_modexp.hip   the modexp precompile: host grouping by modulus width, one launch per class
 //   gsv_ethash.hip   ethash: dataset items, hashimotoLight / Full, VerifySeal, Seal; the epochs' caches and datasets
 //   gsv_block_header.hip  types.Header hashes, CalcDifficulty, Ethash.VerifyHeaders: the launch chain around the seal
+//   gsv_receipt.hip  bloom9, CreateBloom and the receipt half of ValidateState: the launch chain around DeriveSha
 //   gsv_trie.hip     chunk root, DeriveSha, Proof of Custody, collation headers
 //   gsv_pairing.hip  BN254 pairing check
 //   gsv_notary.hip   notary validation, shard partition + RCCL all-gather
@@ -196,8 +197,8 @@ struct gsv_ctx {
     struct Pending { int kid; hipEvent_t a, b; };
     std::vector<Pending> pending;
     std::vector<hipEvent_t> free_events;
-    double total_ms[GSV_K_SUMMIT] = {0};
-    long launches[GSV_K_SUMMIT] = {0};
+    double total_ms[GSV_K_CREST] = {0};
+    long launches[GSV_K_CREST] = {0};
     std::mutex tmu;
     std::vector<hipEvent_t> open_ev;  // timer events opened by launch hooks
     hipStream_t cur_stream = nullptr;  // stream of the shape run in progress (launch hooks)
@@ -359,6 +360,10 @@ int chunk_run(gsv_ctx* c, const Shape& s, const ChunkLaunch& cl, const uint8_t* 
 uint64_t stage_offsets(const uint64_t* off, size_t n, std::vector<uint64_t>& st, std::vector<uint64_t>& en);
 int stage_bodies(gsv_ctx* c, uint8_t* d_b, const uint8_t* bodies, const uint64_t* off, size_t n,
                  const std::vector<uint64_t>& st, const std::vector<uint64_t>& en);
+// generic DeriveSha as a shape, for a host form that runs it between launches of its own (gsv_receipt.hip): item k
+// = d_vals[voff[k] .. voff[k+1]), list i = items [list_off[i], list_off[i+1])
+int derive_prepare(gsv_ctx* c, Shape& s, const uint64_t* voff, const uint64_t* list_off, size_t n, Layout& L);
+int derive_launch(gsv_ctx* c, const Shape& s, const uint8_t* d_vals, uint8_t* d_roots, hipStream_t st);
 // ---- gsv_ethash.hip: VerifySeal's checks over host arrays grouped by epoch (gsv_ethash_verify_seal_batch), for a
 // caller that holds the context's lock `lk` (it may be dropped and retaken while a cache is generated).  Uses the
 // arena and synchronises.

@@ -193,6 +193,25 @@ hipError_t launch_block_header_merge(const uint8_t* d_pre, const uint8_t* d_seal
 hipError_t launch_calc_difficulty(uint8_t* d_work, uint32_t n, const bh::Config& cfg, const uint64_t* d_time,
                                   uint8_t* d_want32, uint8_t* d_status, hipStream_t st);
 
+// receipt.hip: the receipt half of ValidateState.  d_work: rc::work_bytes(n, vals_bytes) bytes (receipt_host.h),
+// 8-byte aligned, its descriptor table zero-filled before the scan; the bloom rows (256 bytes each, any alignment)
+// zero-filled before the bloom launch; d_receipt_bloom null: not wanted
+hipError_t launch_receipt_scan(const uint8_t* d_vals, const uint64_t* d_voff, uint32_t n, const uint64_t* d_list_off,
+                               uint32_t n_lists, uint64_t vals_bytes, uint8_t* d_work, uint8_t* d_receipt_status,
+                               hipStream_t st);
+hipError_t launch_receipt_bloom(const uint8_t* d_vals, const uint64_t* d_voff, uint32_t n, uint64_t vals_bytes,
+                                const uint8_t* d_work, uint8_t* d_list_bloom, uint8_t* d_receipt_bloom,
+                                hipStream_t st);
+hipError_t launch_receipt_lists(const uint64_t* d_list_off, uint32_t n_lists, uint32_t n, uint64_t vals_bytes,
+                                const uint8_t* d_work, const uint8_t* d_receipt_status, uint8_t* d_list_bloom,
+                                uint64_t* d_gas_used, uint8_t* d_list_status, hipStream_t st);
+hipError_t launch_receipt_check(const uint8_t* d_list_status, uint32_t n_lists, const uint8_t* d_list_bloom,
+                                uint8_t* d_root32, const uint64_t* d_gas_used, const uint8_t* d_want_bloom,
+                                const uint8_t* d_want_root32, const uint64_t* d_want_gas, uint8_t* d_status,
+                                hipStream_t st);
+// bloom9's three bit numbers per message: d_idx n x 3 uint16
+hipError_t launch_bloom9(const uint8_t* d_data, const uint64_t* d_off, uint32_t n, uint16_t* d_idx, hipStream_t st);
+
 // collation.hip: CollationHeader.Hash() with ProposerSignature empty (k_header_hash alone: the hash the
 // proposer signs), no nil fields
 hipError_t launch_header_hash_unsigned(const uint8_t* d_sid32, const uint8_t* d_root32, const uint8_t* d_per32,

@@ -232,6 +232,19 @@ int header_shape(gsv_ctx*, Shape& s, size_t n, Layout& L) {
 
 }  // namespace
 
+namespace gsv {
+namespace api {
+
+int derive_prepare(gsv_ctx* c, Shape& s, const uint64_t* voff, const uint64_t* list_off, size_t n, Layout& L) {
+    return derive_shape(c, s, voff, list_off, n, L);
+}
+int derive_launch(gsv_ctx* c, const Shape& s, const uint8_t* d_vals, uint8_t* d_roots, hipStream_t st) {
+    return derive_run(c, s, d_vals, d_roots, st);
+}
+
+}  // namespace api
+}  // namespace gsv
+
 extern "C" {
 
 // ------------------------------------------------------------------ chunk root

@@ -295,6 +295,31 @@ struct BlockMergeStage {
     B8 pre, seal, post, out;
     BlockMergeStage(Layout& L, size_t n) : pre(L.buf(n)), seal(L.buf(n)), post(L.buf(n)), out(L.buf(n)) {}
 };
+// gsv_bloom9_batch: the messages and their rebased table in, three bit numbers per message out
+struct Bloom9Stage {
+    B8 data;
+    Buf<uint64_t> off;
+    Buf<uint16_t> idx;
+    Bloom9Stage(Layout& L, size_t bytes, size_t n)
+        : data(L.buf(bytes + 8)), off(L.buf<uint64_t>((n + 1) * 8)), idx(L.buf<uint16_t>(n * 6)) {}
+};
+// gsv_receipts_verify_batch: the receipts' bytes and both rebased tables, the work area of the _dev chain
+// (gsv_receipts_work_bytes), what the chain writes, and the header's three values where the caller gave them
+struct ReceiptStage {
+    B8 vals;
+    Buf<uint64_t> voff, loff;
+    B8 work, rstatus, lbloom, roots;
+    Buf<uint64_t> gas;
+    B8 lstatus, status, want_bloom, want_root;
+    Buf<uint64_t> want_gas;
+    ReceiptStage(Layout& L, size_t bytes, size_t n, size_t n_lists, size_t work_bytes, bool has_bloom, bool has_root,
+                 bool has_gas)
+        : vals(L.buf(bytes + 16)), voff(L.buf<uint64_t>((n + 1) * 8)), loff(L.buf<uint64_t>((n_lists + 1) * 8)),
+          work(L.buf(work_bytes)), rstatus(L.buf(n)), lbloom(L.buf(n_lists * 256)), roots(L.buf(n_lists * 32)),
+          gas(L.buf<uint64_t>(n_lists * 8)), lstatus(L.buf(n_lists)), status(L.buf(n_lists)),
+          want_bloom(L.buf(n_lists * 256, has_bloom)), want_root(L.buf(n_lists * 32, has_root)),
+          want_gas(L.buf<uint64_t>(n_lists * 8, has_gas)) {}
+};
 
 }  // namespace api
 }  // namespace gsv

@@ -1317,6 +1317,89 @@ def _block_header_merge_dev(self, pre_t, seal_t, seals_t, post_t, status_t, n=No
                                                  n, _tptr(status_t), _sp(stream)))
 
 
+def _bloom9_batch(self, items) -> np.ndarray:
+    """bloom9's three bit numbers of each byte string (gsv.h gsv_bloom9_batch): (n, 3) uint16"""
+    items = [bytes(x) for x in items]
+    n = len(items)
+    flat, off = _pack(items)
+    out = np.zeros((n, 3), np.uint16)
+    check(_lib.load().gsv_bloom9_batch(self._h, _ptr(flat), _ptr(off), n, _ptr(out)))
+    return out
+
+
+def _bloom9_batch_dev(self, data_t, off_t, idx_t, n=None, stream=None):
+    """data_t: torch uint8 CUDA tensor; off_t: n + 1 int64 offsets on the device; idx_t: (n, 3) int16 rows"""
+    n = int(off_t.numel()) - 1 if n is None else int(n)
+    check(_lib.load().gsv_bloom9_batch_dev(self._h, _tptr(data_t), _tptr(off_t), n, _tptr(idx_t), _sp(stream)))
+
+
+def _receipt_tables(lists):
+    """lists of receipt RLPs -> (flat uint8, voff uint64[receipts + 1], list_off uint64[lists + 1])"""
+    items = [bytes(x) for lst in lists for x in lst]
+    flat, voff = _pack(items)
+    list_off = np.zeros(len(lists) + 1, np.uint64)
+    list_off[1:] = np.cumsum([len(lst) for lst in lists])
+    return flat, voff, list_off
+
+
+def _rows_or_none(a, n, width, what):
+    if a is None:
+        return None
+    a = np.ascontiguousarray(np.frombuffer(b"".join(bytes(x) for x in a), np.uint8) if isinstance(a, (list, tuple))
+                             else a, np.uint8).reshape(-1)
+    if a.size != n * width:
+        raise ValueError(f"receipts: one {what} of {width} bytes per list")
+    return a
+
+
+def _receipts_verify_batch(self, lists, want_bloom=None, want_root=None, want_gas=None):
+    """The receipt half of ValidateState over lists of RLP-encoded receipts (gsv.h gsv_receipts_verify_batch).
+    want_bloom (n x 256 bytes), want_root (n x 32), want_gas (n integers): each None skips that compare.  Returns
+    (status (n,), receipt status (receipts,), blooms (n, 256), roots (n, 32), gas used (n,) uint64)."""
+    lists = [list(lst) for lst in lists]
+    n = len(lists)
+    flat, voff, list_off = _receipt_tables(lists)
+    nr = int(list_off[-1])
+    wb = _rows_or_none(want_bloom, n, 256, "bloom")
+    wr = _rows_or_none(want_root, n, 32, "receipt hash")
+    wg = None
+    if want_gas is not None:
+        wg = np.ascontiguousarray(want_gas, np.uint64).reshape(-1)
+        if wg.shape[0] != n:
+            raise ValueError("receipts: one gas-used value per list")
+    st = np.zeros(n, np.uint8)
+    rst = np.zeros(nr, np.uint8)
+    bloom = np.zeros((n, 256), np.uint8)
+    root = np.zeros((n, 32), np.uint8)
+    gas = np.zeros(n, np.uint64)
+    check(_lib.load().gsv_receipts_verify_batch(self._h, _ptr(flat), _ptr(voff), _ptr(list_off), n, _ptr(wb), _ptr(wr),
+                                                _ptr(wg), _ptr(rst), _ptr(bloom), _ptr(root), _ptr(gas), _ptr(st)))
+    return st, rst, bloom, root, gas
+
+
+def receipts_work_bytes(n_receipts: int, vals_bytes: int) -> int:
+    """gsv_receipts_work_bytes: the work area of receipts_bloom_dev (0: past the call's bounds)"""
+    return int(_lib.load().gsv_receipts_work_bytes(int(n_receipts), int(vals_bytes)))
+
+
+def _receipts_bloom_dev(self, vals_t, voff_t, n_receipts: int, list_off_t, n_lists: int, vals_bytes: int, work_t,
+                        receipt_status_t, receipt_bloom_t, list_bloom_t, gas_used_t, list_status_t, stream=None):
+    """Decode + blooms over torch CUDA tensors (gsv.h gsv_receipts_bloom_dev): both offset tables on the device.
+    Only enqueues on `stream`: memset nodes and three launches."""
+    check(_lib.load().gsv_receipts_bloom_dev(self._h, _tptr(vals_t), _tptr(voff_t), int(n_receipts), _tptr(list_off_t),
+                                             int(n_lists), int(vals_bytes), _tptr(work_t), _tptr(receipt_status_t),
+                                             _tptr(receipt_bloom_t), _tptr(list_bloom_t), _tptr(gas_used_t),
+                                             _tptr(list_status_t), _sp(stream)))
+
+
+def _receipts_check_dev(self, list_status_t, list_bloom_t, root_t, gas_used_t, want_bloom_t, want_root_t, want_gas_t,
+                        n_lists: int, status_t, stream=None):
+    """gas used, bloom and receipt root against the header's (gsv.h gsv_receipts_check_dev): one launch"""
+    check(_lib.load().gsv_receipts_check_dev(self._h, _tptr(list_status_t), _tptr(list_bloom_t), _tptr(root_t),
+                                             _tptr(gas_used_t), _tptr(want_bloom_t), _tptr(want_root_t),
+                                             _tptr(want_gas_t), int(n_lists), _tptr(status_t), _sp(stream)))
+
+
 def _arena_read(self, off, n):
     """Test hook (gsv.h gsv_ctx_arena_read): n bytes of the staging arena from `off`, as they are now."""
     out = np.zeros(n, np.uint8)
@@ -1368,6 +1451,11 @@ Context.calc_difficulty_batch = _calc_difficulty_batch
 Context.ethash_verify_headers_batch = _ethash_verify_headers_batch
 Context.block_header_rules_dev = _block_header_rules_dev
 Context.block_header_merge_dev = _block_header_merge_dev
+Context.bloom9_batch = _bloom9_batch
+Context.bloom9_batch_dev = _bloom9_batch_dev
+Context.receipts_verify_batch = _receipts_verify_batch
+Context.receipts_bloom_dev = _receipts_bloom_dev
+Context.receipts_check_dev = _receipts_check_dev
 Context.modexp_batch = _modexp_batch
 Context.modexp_batch_dev = _modexp_batch_dev
 Context._arena_read = _arena_read

@@ -47,6 +47,10 @@ ST_INVALID_NUMBER = 29
 ST_BAD_PRO_DAO_EXTRA = 30
 ST_BAD_NO_DAO_EXTRA = 31
 ST_FORK_HASH = 32
+ST_RECEIPT_STATUS = 33
+ST_GAS_USED_MISMATCH = 34
+ST_INVALID_BLOOM = 35
+ST_INVALID_RECEIPT_ROOT = 36
 
 # a short text per per-item status: the reference's error string where it has one (include/gsv.h names
 # the sources)
@@ -84,6 +88,10 @@ STATUS_STRINGS = {
     ST_BAD_PRO_DAO_EXTRA: "bad DAO pro-fork extra-data",
     ST_BAD_NO_DAO_EXTRA: "bad DAO no-fork extra-data",
     ST_FORK_HASH: "homestead gas reprice fork: wrong hash",
+    ST_RECEIPT_STATUS: "invalid receipt status",
+    ST_GAS_USED_MISMATCH: "invalid gas used",
+    ST_INVALID_BLOOM: "invalid bloom",
+    ST_INVALID_RECEIPT_ROOT: "invalid receipt root hash",
 }
 
 SIGNER_EIP155 = 0
@@ -122,7 +130,13 @@ K_PEAK = 23  # GSV_K_PEAK: pinned; the ids behind it follow
 K_BLOCK_HEADER = 23
 K_BLOCK_RULES = 24
 K_BLOCK_MERGE = 25
-K_SUMMIT = 26  # GSV_K_SUMMIT: gsv_ctx_kernel_time takes every id below it
+K_SUMMIT = 26  # GSV_K_SUMMIT: pinned; the ids behind it follow
+K_RECEIPT_SCAN = 26
+K_RECEIPT_BLOOM = 27
+K_RECEIPT_LISTS = 28
+K_RECEIPT_CHECK = 29
+K_BLOOM9 = 30
+K_CREST = 31  # GSV_K_CREST: gsv_ctx_kernel_time takes every id below it
 
 ETHASH_MAX_CACHES = 3  # GSV_ETHASH_MAX_CACHES: epoch caches a context keeps for the ethash host forms
 ETHASH_MAX_DATASETS = 2  # GSV_ETHASH_MAX_DATASETS: epoch datasets a context keeps for the full and seal forms
@@ -267,6 +281,12 @@ SIGNATURES = [
     ("gsv_block_header_rules_dev", ctypes.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _u64, _vp, _vp, _vp, _vp, _vp, _vp,
                                                   _vp, _vp, _vp, _vp, _vp]),
     ("gsv_block_header_merge_dev", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    ("gsv_bloom9_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp]),
+    ("gsv_bloom9_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    ("gsv_receipts_work_bytes", _sz, [_sz, _u64]),
+    ("gsv_receipts_bloom_dev", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("gsv_receipts_check_dev", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    ("gsv_receipts_verify_batch", ctypes.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("gsv_chunk_root_prepare", ctypes.c_int, [_vp, _vp, _sz]),
     ("gsv_bn256_pairing_prepare", ctypes.c_int, [_vp, _vp, _sz]),
     ("gsv_notary_prepare", ctypes.c_int, [_vp, _vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_uint32]),

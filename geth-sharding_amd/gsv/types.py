@@ -8,6 +8,11 @@
 
     HeaderHashes(rlps)           Header.Hash() and Header.HashNoNonce() (core/types/block.go:99-122) over a batch
 
+    Bloom9(items)                bloom9 / calcBloomIndexes (core/types/bloom9.go:115-127): three bit numbers each
+    BloomLookup(bloom, topic)    :131-136; BloomLookupBatch(blooms, topics) over pairs
+    LogsBloom(receipt_rlps)      :103-113 per RLP-encoded receipt
+    CreateBloom(receipt_rlps)    :94-101 over one list; CreateBloomBatch(lists) over many
+
 The inverse, types.Sender over a batch, is Context.tx_sender_batch with the signer's kind and chain_id.
 Transactions travel as their RLP encoding (rlp.EncodeToBytes(tx)), signed or not; an unsigned
 NewTransaction carries V = R = S = 0.
@@ -84,4 +89,60 @@ def HeaderHashes(rlps, ctx=None):
     return (ctx or default_context()).block_header_hash_batch(rlps)
 
 
-__all__ = ["HeaderHashes", "EIP155Signer", "HomesteadSigner", "FrontierSigner", "SignTx", "SignTxBatch", "ErrInvalidKey", "ErrBadRLP"]
+BloomByteLength = 256  # bloom9.go:33
+
+
+class ErrBadReceipt(ValueError):
+    """a receipt that rlp.DecodeBytes refuses, or whose status field setStatus refuses (receipt.go:116-128)"""
+
+
+def Bloom9(items, ctx=None):
+    """bloom9 of each byte string (bloom9.go:115-127) as its three bit numbers: (n, 3) uint16, bit b being byte
+    255 - b // 8 under mask 1 << (b % 8) of a Bloom."""
+    return (ctx or default_context()).bloom9_batch(items)
+
+
+def _bloom_rows(blooms):
+    rows = np.frombuffer(b"".join(bytes(b) for b in blooms), np.uint8).reshape(len(blooms), -1)
+    if rows.shape[0] and rows.shape[1] != BloomByteLength:
+        raise ValueError("a Bloom is 256 bytes")
+    return rows.reshape(-1, BloomByteLength)
+
+
+def BloomLookupBatch(blooms, topics, ctx=None):
+    """BloomLookup(blooms[i], topics[i]) (bloom9.go:131-136): (n,) bool; the hashes run on the GPU, the three bit
+    tests per pair on the host."""
+    rows = _bloom_rows(blooms)
+    idx = Bloom9(topics, ctx).astype(np.int64)
+    if idx.shape[0] != rows.shape[0]:
+        raise ValueError("one topic per bloom")
+    k = np.arange(rows.shape[0])[:, None]
+    return ((rows[k, 255 - (idx >> 3)] >> (idx & 7)) & 1).all(axis=1)
+
+
+def BloomLookup(bloom, topic, ctx=None) -> bool:
+    return bool(BloomLookupBatch([bloom], [topic], ctx)[0])
+
+
+def CreateBloomBatch(lists, ctx=None):
+    """types.CreateBloom (bloom9.go:94-101) of each list of RLP-encoded receipts: (blooms (n, 256) uint8, status
+    (n,): ST_OK, or the first failing receipt's ST_BAD_RLP / ST_RECEIPT_STATUS with a zero row)."""
+    st, _, bloom, _, _ = (ctx or default_context()).receipts_verify_batch(lists)
+    return bloom, st
+
+
+def CreateBloom(receipt_rlps, ctx=None) -> bytes:
+    """types.CreateBloom over one block's receipts; ErrBadReceipt where one of them does not decode"""
+    bloom, st = CreateBloomBatch([receipt_rlps], ctx)
+    if st[0] != _lib.ST_OK:
+        raise ErrBadReceipt(_lib.STATUS_STRINGS[int(st[0])])
+    return bloom[0].tobytes()
+
+
+def LogsBloom(receipt_rlps, ctx=None):
+    """types.LogsBloom(receipt.Logs) (bloom9.go:103-113) per RLP-encoded receipt: (rows (n, 256) uint8, status (n,))"""
+    return CreateBloomBatch([[r] for r in receipt_rlps], ctx)
+
+
+__all__ = ["Bloom9", "BloomLookup", "BloomLookupBatch", "LogsBloom", "CreateBloom", "CreateBloomBatch", "ErrBadReceipt",
+           "HeaderHashes", "EIP155Signer", "HomesteadSigner", "FrontierSigner", "SignTx", "SignTxBatch", "ErrInvalidKey", "ErrBadRLP"]

@@ -72,6 +72,10 @@
  *   gsv_calc_difficulty_batch  <- ethash.CalcDifficulty (consensus/ethash/consensus.go:297-459)
  *   gsv_ethash_verify_headers_batch <- Ethash.VerifyHeaders (consensus/ethash/consensus.go:90-166): verifyHeaderWorker
  *                                 and verifyHeader (:223-285) with uncle = false, VerifySeal included
+ *   gsv_bloom9_batch           <- bloom9 (core/types/bloom9.go:115-127), behind BloomLookup (:131-136)
+ *   gsv_receipts_verify_batch  <- types.CreateBloom (bloom9.go:94-113), the receipt root and the three receipt
+ *                                 compares of BlockValidator.ValidateState (core/block_validator.go:80-95) over
+ *                                 RLP-encoded receipts (core/types/receipt.go:67-128)
  *
  * Conventions
  *   - Return value: GSV_SUCCESS (0) or a negative GSV_E_* API/HIP error. A bad ITEM never fails
@@ -154,6 +158,11 @@ extern "C" {
 #define GSV_ST_BAD_PRO_DAO_EXTRA 30  /* misc.ErrBadProDAOExtra         consensus/misc/dao.go:32, :58-61 */
 #define GSV_ST_BAD_NO_DAO_EXTRA 31   /* misc.ErrBadNoDAOExtra          consensus/misc/dao.go:36, :62-66 */
 #define GSV_ST_FORK_HASH 32          /* "homestead gas reprice fork"   consensus/misc/forks.go:36-39 */
+/* receipts (gsv_receipts_verify_batch), in the order the receipt half of ValidateState tests them */
+#define GSV_ST_RECEIPT_STATUS 33       /* "invalid receipt status"     core/types/receipt.go:116-128 */
+#define GSV_ST_GAS_USED_MISMATCH 34    /* "invalid gas used"           core/block_validator.go:82-84 */
+#define GSV_ST_INVALID_BLOOM 35        /* "invalid bloom"              core/block_validator.go:87-90 */
+#define GSV_ST_INVALID_RECEIPT_ROOT 36 /* "invalid receipt root hash"  core/block_validator.go:92-95 */
 
 /* signer kinds for gsv_tx_sender_batch and gsv_tx_sign_batch (core/types/transaction_signing.go) */
 #define GSV_SIGNER_EIP155 0
@@ -228,6 +237,14 @@ int gsv_ctx_set_timing(gsv_ctx *ctx, int enable);
 #define GSV_K_BLOCK_RULES 24  /* verifyHeader's rules around the seal, or CalcDifficulty alone: one launch per call */
 #define GSV_K_BLOCK_MERGE 25  /* the merge of the pre-seal, seal and post-seal statuses: one launch per call */
 #define GSV_K_SUMMIT 26
+/* Ids added behind GSV_K_SUMMIT (pinned like the seven before it); gsv_ctx_kernel_time takes every id below
+ * GSV_K_CREST. */
+#define GSV_K_RECEIPT_SCAN 26  /* receipts: the strict decode, one descriptor per bloom item: one launch per call */
+#define GSV_K_RECEIPT_BLOOM 27 /* receipts: one Keccak-256 per log address and topic, the bloom rows: one launch */
+#define GSV_K_RECEIPT_LISTS 28 /* receipts: each list's first failure and gas used: one launch per call */
+#define GSV_K_RECEIPT_CHECK 29 /* receipts: gas used, bloom and root against the header's: one launch per call */
+#define GSV_K_BLOOM9 30        /* bloom9 over byte strings: one launch per call */
+#define GSV_K_CREST 31
 /* total milliseconds and launch count accumulated for kernel `kid` since the last reset */
 int gsv_ctx_kernel_time(gsv_ctx *ctx, int kid, double *total_ms, long *launches);
 int gsv_ctx_reset_timing(gsv_ctx *ctx);
@@ -947,6 +964,91 @@ int gsv_derive_sha_batch(gsv_ctx *ctx, const uint8_t *vals, const uint64_t *voff
 int gsv_derive_sha_prepare(gsv_ctx *ctx, const uint64_t *voff, const uint64_t *list_off, size_t n_lists);
 int gsv_derive_sha_batch_dev(gsv_ctx *ctx, const uint8_t *d_vals, const uint64_t *voff, const uint64_t *list_off,
                              size_t n_lists, uint8_t *d_root32_out, void *stream);
+
+/* ---- logs bloom and receipts: the receipt half of BlockValidator.ValidateState (core/block_validator.go:80-95) ----
+ * bloom9 (core/types/bloom9.go:115-127): Keccak-256 of a byte string; its three bits are the low 11 bits of the
+ * big-endian byte pairs 0-1, 2-3 and 4-5 of the digest.  Bit b of a 2,048-bit Bloom lies in byte 255 - b / 8 under
+ * mask 1 << (b % 8) (the big.Int layout, core/bloombits/generator.go:64-70).
+ *   gsv_bloom9_batch: message i = data[off[i] .. off[i+1]), any length; idx_out[3 i .. 3 i + 3) = its three bit
+ *   numbers.  What BloomLookup and a bloombits filter test.  The _dev form takes device arrays (the n + 1 offsets
+ *   included; d_idx_out 2-byte aligned) and only enqueues one launch (GSV_K_BLOOM9): no allocation, no
+ *   synchronisation, no prepare call, capturable.  n == 0: success, nothing enqueued. */
+int gsv_bloom9_batch(gsv_ctx *ctx, const uint8_t *data, const uint64_t *off, size_t n, uint16_t *idx_out);
+int gsv_bloom9_batch_dev(gsv_ctx *ctx, const uint8_t *d_data, const uint64_t *d_off, size_t n, uint16_t *d_idx_out,
+                         void *stream);
+/* Receipts.  Receipt k = vals[voff[k] .. voff[k+1]) is Receipts.GetRlp(k), the consensus encoding
+ * rlp([PostStateOrStatus, CumulativeGasUsed, Bloom, Logs]) (core/types/receipt.go:67-73, :98-100); list i (one
+ * block) holds receipts [list_off[i], list_off[i+1]), as gsv_derive_sha_batch takes its items.
+ *
+ * Decode, as rlp.DecodeBytes into types.Receipt (receipt.go:104-114, core/types/log.go:65-95): a list of exactly four
+ * items; PostStateOrStatus a string; CumulativeGasUsed a uint64 (no leading zero byte, at most 8 bytes); Bloom of
+ * exactly 256 bytes; Logs a list of lists of exactly three items: Address of exactly 20 bytes, Topics a list of any
+ * number of 32-byte strings (the decoder has no cap of four), Data a string.  Every length in its shortest form, a
+ * single byte below 0x80 as itself, no element missing or left over, no length past its list or the input, no byte
+ * behind the list, no empty input.  What the reference's decoder refuses is GSV_ST_BAD_RLP.  A receipt that
+ * decodes and whose status field is none of the empty string, the byte 01 or 32 bytes is GSV_ST_RECEIPT_STATUS
+ * (setStatus, receipt.go:116-128); as in the reference, that is judged before bytes behind the list are.  The
+ * Bloom field of a receipt is carried, not checked: ValidateState compares the block's bloom only.
+ *
+ * Bloom.  LogsBloom (bloom9.go:103-113) ORs bloom9 of each log's Address and of each of its Topics; CreateBloom
+ * (:94-101) ORs that over a list's receipts.  The decoder accepts canonical encodings only, so a receipt that
+ * decodes re-encodes to the same bytes, and the receipt root is gsv_derive_sha_batch over the very same vals.
+ *
+ * Per list, in this order; the first that applies is the status:
+ *    1. the status of the first receipt of the list that is not GSV_ST_OK.  OURS: the reference never gets as
+ *       far as ValidateState with a receipt that does not decode.  Such a list has a zero bloom row, a zero root
+ *       row and gas used 0.
+ *    2. gas used != want_gas_used[i]                     GSV_ST_GAS_USED_MISMATCH   (block_validator.go:82-84)
+ *    3. bloom row != want_bloom256 row i                 GSV_ST_INVALID_BLOOM       (:87-90)
+ *    4. receipt root != want_root32 row i                GSV_ST_INVALID_RECEIPT_ROOT (:92-95)
+ *    5. else                                             GSV_ST_OK
+ * Gas used is the last receipt's CumulativeGasUsed, 0 for an empty list (an empty list has a zero bloom and
+ * emptyRoot).  The state root (IntermediateRoot, :98-100) needs the state database and stays with the caller.
+ *
+ * Host form.  gsv_receipts_verify_batch stages, runs the chain below with DeriveSha in the middle and copies back.
+ * Each want_* may be NULL: that compare is skipped, so with all three NULL the call is CreateBloom plus the
+ * receipt root.  Outputs, each NULL or its full size: receipt_status (one byte per receipt of
+ * [list_off[0], list_off[n_lists])), list_bloom256 (n_lists x 256), root32 (n_lists x 32), gas_used (n_lists);
+ * status (n_lists bytes) is required.  n_lists == 0: success, nothing launched.  GSV_E_INVALID_ARG before any HIP
+ * call: a NULL context, table or status, a table that steps backwards, 2^31 receipts or more; GSV_E_TOO_LARGE: a
+ * receipt of 2^32 bytes or more, or more than 2^40 bytes of receipts.
+ *
+ * Device-resident forms.  Both only enqueue on `stream` (NULL = the context stream): no allocation, no
+ * synchronisation, no prepare call, capturable.  The caller runs gsv_derive_sha_batch_dev between them.
+ *   bloom: memset nodes over the work area's descriptor table and the bloom rows, then three launches:
+ *          k_receipt_scan (GSV_K_RECEIPT_SCAN), k_receipt_bloom (GSV_K_RECEIPT_BLOOM: one lane per bloom ITEM, so
+ *          a receipt of hundreds of logs costs what its items cost) and k_receipt_lists (GSV_K_RECEIPT_LISTS).
+ *          d_voff: n_receipts + 1 ascending offsets into d_vals, in HBM; d_voff[0] may be nonzero and d_vals may
+ *          have any alignment.  d_list_off: n_lists + 1 ascending receipt indices in [0, n_receipts], in HBM; a
+ *          receipt no list holds is decoded and joins no row.  Both tables 8-byte aligned.  vals_bytes: the
+ *          caller's bound on d_voff[n_receipts] - d_voff[0], at most 2^40.  OURS: a receipt that reaches past
+ *          vals_bytes (or starts before d_voff[0], or ends before it starts, or is 2^32 bytes or longer) is
+ *          GSV_ST_BAD_RLP unread, and no byte outside d_work is ever written for it.  d_work:
+ *          gsv_receipts_work_bytes(n_receipts, vals_bytes) bytes of the caller's, 8-byte aligned (0: past the
+ *          bounds).  Writes d_receipt_status (n_receipts), d_receipt_bloom256 (n_receipts x 256, may be NULL),
+ *          d_list_bloom256 (n_lists x 256), d_gas_used (n_lists, 8-byte aligned), d_list_status (n_lists: rule 1
+ *          alone).  Byte outputs have any alignment: the bloom rows are written by dword atomics on the aligned
+ *          dwords that hold their bytes, which OR zeros into the up to three bytes in front of and behind them.
+ *          The kernels read no byte outside d_vals[d_voff[0] .. d_voff[0] + vals_bytes) but for the other bytes
+ *          of the aligned dwords that hold an item's first and last byte.
+ *   check: one launch (GSV_K_RECEIPT_CHECK): rules 1-5 over d_list_status_in, d_list_bloom256, d_root32 and
+ *          d_gas_used against the d_want_* arrays (each may be NULL; d_want_gas_used 8-byte aligned).  d_root32 is
+ *          read and, for a list under rule 1, overwritten with zeros.
+ * GSV_E_INVALID_ARG: a NULL context or required array, a misaligned table, d_work or gas array, n_receipts or
+ * n_lists above 2^31 - 1, vals_bytes above 2^40.  n_lists == 0: success, nothing enqueued. */
+size_t gsv_receipts_work_bytes(size_t n_receipts, uint64_t vals_bytes);
+int gsv_receipts_bloom_dev(gsv_ctx *ctx, const uint8_t *d_vals, const uint64_t *d_voff, size_t n_receipts,
+                           const uint64_t *d_list_off, size_t n_lists, uint64_t vals_bytes, uint8_t *d_work,
+                           uint8_t *d_receipt_status, uint8_t *d_receipt_bloom256, uint8_t *d_list_bloom256,
+                           uint64_t *d_gas_used, uint8_t *d_list_status, void *stream);
+int gsv_receipts_check_dev(gsv_ctx *ctx, const uint8_t *d_list_status_in, const uint8_t *d_list_bloom256,
+                           uint8_t *d_root32, const uint64_t *d_gas_used, const uint8_t *d_want_bloom256,
+                           const uint8_t *d_want_root32, const uint64_t *d_want_gas_used, size_t n_lists,
+                           uint8_t *d_status, void *stream);
+int gsv_receipts_verify_batch(gsv_ctx *ctx, const uint8_t *vals, const uint64_t *voff, const uint64_t *list_off,
+                              size_t n_lists, const uint8_t *want_bloom256, const uint8_t *want_root32,
+                              const uint64_t *want_gas_used, uint8_t *receipt_status, uint8_t *list_bloom256,
+                              uint8_t *root32, uint64_t *gas_used, uint8_t *status);
 
 /* ---- Proof of Custody (sharding/collation.go:124-136) ----
  * poc32_out[i] = DeriveSha(Chunks(salt||b0||salt||b1||...)) over body i = bodies[off[i] .. off[i+1])
