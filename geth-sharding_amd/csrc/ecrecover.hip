@@ -30,16 +30,68 @@
 //     address.
 #include "opcount.cuh"
 #include "recover_dev.cuh"  // before the other secp256k1 headers (secp256k1_glv.cuh)
+#include "secp256k1_rinv.cuh"
 #include "secp256k1_sign.cuh"
 
 namespace gsv {
 
 // ---------------------------------------------------------------------------- kernels
+// r^-1 mod n for every signature of a batch, RINV_K of them from one inversion per lane
+// (secp256k1_rinv.cuh), written as 8 little-endian words into the first 32 bytes of the item's row of
+// pub65: the caller's own output, which k_ecrecover<true> reads back and overwrites only at its very end,
+// so no workspace and no state outlive the call.  Wave g takes items [64 RINV_K g, 64 RINV_K (g + 1)),
+// lane l of it the items l, l + 64, ...: neighbouring lanes touch neighbouring rows.  The prefix products
+// are parked in the same rows between the two sweeps.  One wave per block, so a batch of 2^20 is one
+// wave per SIMD.
+struct RinvRows {
+    const uint8_t* sig;  // the lane's first signature
+    uint8_t* pub;        // the lane's first row of pub65
+    static constexpr size_t STEP = 64 * 65;
+    GSV_DI void get(uint32_t i, sc& x) const {
+        const uint8_t* p = sig + i * STEP;
+#pragma unroll
+        for (int k = 0; k < 8; k++) x.v[k] = ld32u(p + 4 * k);  // big-endian, as in the signature
+    }
+    GSV_DI void value(sc& x) const {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            uint32_t lo = __builtin_bswap32(x.v[7 - k]), hi = __builtin_bswap32(x.v[k]);
+            x.v[k] = lo;
+            x.v[7 - k] = hi;
+        }
+    }
+    GSV_DI void put(uint32_t i, const sc& x) const {
+#pragma unroll
+        for (int k = 0; k < 8; k++) st32u(pub + i * STEP + 4 * k, x.v[k]);
+    }
+    GSV_DI void take(uint32_t i, sc& x) const {
+#pragma unroll
+        for (int k = 0; k < 8; k++) x.v[k] = ld32u(pub + i * STEP + 4 * k);
+    }
+};
+
+__global__ __launch_bounds__(64) void k_rinv_batch(const uint8_t* __restrict__ sig65, uint32_t n,
+                                                   uint8_t* __restrict__ pub65) {
+    size_t first = (size_t)blockIdx.x * (64 * RINV_K) + threadIdx.x;
+    if (first >= n) return;
+    size_t left = (n - first + 63) / 64;  // the lane's items below n: first + 64 (left - 1) < n
+    RinvRows rows{sig65 + first * 65, pub65 + first * 65};
+    sc_batch_inverse(rows, left < (size_t)RINV_K ? (uint32_t)left : (uint32_t)RINV_K);
+}
+
+// pub65 of k_ecrecover<true> is read (the stashed r^-1) before it is written: not __restrict__
+template <bool RINV_GIVEN>
+struct PubRows { typedef uint8_t* __restrict__ type; };
+template <>
+struct PubRows<true> { typedef uint8_t* type; };
+
 // 2 waves/SIMD: two 256-thread blocks per CU share its 160 KiB LDS (72 KiB GLV table each)
+// RINV_GIVEN: pub65 is not null and k_rinv_batch has run on it
+template <bool RINV_GIVEN>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GSV_ECR_WAVES, GSV_ECR_WAVES))) void k_ecrecover(const uint8_t* __restrict__ msg32,
                                                    const uint8_t* __restrict__ sig65, uint32_t n,
                                                    const uint4* __restrict__ gtab,
-                                                   uint8_t* __restrict__ pub65,
+                                                   typename PubRows<RINV_GIVEN>::type pub65,
                                                    uint8_t* __restrict__ addr20,
                                                    uint8_t* __restrict__ status) {
     GSV_LTAB_DECL;
@@ -52,7 +104,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GSV_ECR_WAV
     load32_be(s, sg + 32);
     uint32_t recid = sg[64];
     fe qx, qy;
-    uint32_t st = recover_core(qx, qy, msg, r, s, recid & 3u, gtab, GSV_LTAB_LANE);
+    uint32_t st = recover_core<RINV_GIVEN>(qx, qy, msg, r, s, recid & 3u, gtab, GSV_LTAB_LANE,
+                                           RINV_GIVEN ? pub65 + (size_t)i * 65 : nullptr);
     if (recid >= 4) st = GSV_ST_INVALID_RECID;
     bool ok = st == GSV_ST_OK;
     store_pub_addr(pub65 ? pub65 + (size_t)i * 65 : nullptr, addr20 ? addr20 + (size_t)i * 20 : nullptr,
@@ -221,7 +274,17 @@ hipError_t launch_gtable_init(uint4* gtab, hipStream_t st) {
 hipError_t launch_ecrecover(const uint8_t* msg32, const uint8_t* sig65, uint32_t n, const uint4* gtab,
                             uint8_t* pub65, uint8_t* addr20, uint8_t* status, hipStream_t st) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_ecrecover, dim3((n + 255) / 256), dim3(256), 0, st, msg32, sig65, n, gtab,
+    if (!pub65) {  // no row to stash r^-1 in: every lane inverts its own r
+        hipLaunchKernelGGL(k_ecrecover<false>, dim3((n + 255) / 256), dim3(256), 0, st, msg32, sig65, n, gtab,
+                           pub65, addr20, status);
+        return hipGetLastError();
+    }
+    constexpr uint32_t PER_WAVE = 64u * RINV_K;
+    hipLaunchKernelGGL(k_rinv_batch, dim3((unsigned)(((uint64_t)n + PER_WAVE - 1) / PER_WAVE)), dim3(64), 0, st,
+                       sig65, n, pub65);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_ecrecover<true>, dim3((n + 255) / 256), dim3(256), 0, st, msg32, sig65, n, gtab,
                        pub65, addr20, status);
     return hipGetLastError();
 }

@@ -267,4 +267,12 @@ constexpr size_t GTAB_ENTRIES = (size_t)COMB_WINDOWS << COMB_BITS;
 constexpr size_t GTAB_ENTRY_BYTES = 80;  // fe9 x[9] y[9] + 2 pad words (secp256k1_comb.cuh gtab_load)
 constexpr size_t GTAB_BYTES = GTAB_ENTRIES * GTAB_ENTRY_BYTES;
 
+// signatures whose r a lane of k_rinv_batch inverts with one safegcd inversion (secp256k1_rinv.cuh):
+// 16 makes a batch of 2^20 one wave per SIMD (measured against 8 and 32: profiles/r11/README.md)
+#ifndef GSV_RINV_K
+#define GSV_RINV_K 16
+#endif
+constexpr int RINV_K = GSV_RINV_K;
+static_assert(RINV_K >= 1 && RINV_K <= 64, "r values per inversion");
+
 }  // namespace gsv

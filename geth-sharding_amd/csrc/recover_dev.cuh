@@ -136,9 +136,13 @@ GSV_DI bool recover_tail_twisted(fe& qx, fe& qy, const gej9& p1, bool p1inf, con
 // ---------------------------------------------------------------------------- recovery core
 // Returns GSV_ST_OK or GSV_ST_RECOVER_FAILED; on OK (qx, qy) is the affine public key.
 // msg/r/s are 256-bit values as little-endian limbs; recid in 0..3.
+// RINV_GIVEN: r^-1 mod n is read from rinv (8 little-endian words at any alignment, < n; written by
+// k_rinv_batch, ecrecover.hip) instead of being computed here; for an r outside [1, n) it is some
+// value < n that the failing status makes irrelevant.
+template <bool RINV_GIVEN = false>
 GSV_DI uint32_t recover_core(fe& qx, fe& qy, const uint32_t msg[8], const uint32_t r[8],
                              const uint32_t s[8], uint32_t recid, const uint4* __restrict__ gtab,
-                             uint32_t* __restrict__ ltab) {
+                             uint32_t* __restrict__ ltab, const uint8_t* rinv = nullptr) {
     bool ok = limbs_lt(r, SN) && limbs_lt(s, SN);
     sc rs, ss, m;
 #pragma unroll
@@ -172,7 +176,12 @@ GSV_DI uint32_t recover_core(fe& qx, fe& qy, const uint32_t msg[8], const uint32
     x = t;
     // u1 = -m / r, u2 = s / r
     sc rn, u1, u2;
-    modinv30_words(rn.v, rs.v, MI30_N);  // r^-1 mod n (safegcd; r != 0 on every valid path)
+    if constexpr (RINV_GIVEN) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) rn.v[i] = ld32u(rinv + 4 * i);
+    } else {
+        modinv30_words(rn.v, rs.v, MI30_N);  // r^-1 mod n (safegcd; r != 0 on every valid path)
+    }
     sc_mul(u1, rn, m);
     sc_neg(u1, u1);
     sc_mul(u2, rn, ss);

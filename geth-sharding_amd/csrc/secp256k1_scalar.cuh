@@ -64,6 +64,14 @@ GSV_DI void limbs_to_be(uint8_t* b, const uint32_t v[8]) {
     }
 }
 
+// a 32-bit word at any alignment (the 65-byte rows of signatures and keys)
+GSV_DI uint32_t ld32u(const uint8_t* p) {
+    uint32_t w;
+    __builtin_memcpy(&w, p, 4);
+    return w;
+}
+GSV_DI void st32u(uint8_t* p, uint32_t w) { __builtin_memcpy(p, &w, 4); }
+
 GSV_DI bool limbs_zero(const uint32_t v[8]) {
     uint32_t o = 0;
 #pragma unroll

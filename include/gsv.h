@@ -312,7 +312,8 @@ int gsv_ripemd160_batch_dev(gsv_ctx *ctx, const uint8_t *d_data, const uint64_t 
 
 /* ---- secp256k1 public-key recovery (A5-A9) ----
  * msg32: n x 32 B message hashes; sig65: n x 65 B [R || S || recid].
- * pub65_out: n x 65 B uncompressed keys (0x04 || X || Y), zeroed for failed items.
+ * pub65_out: n x 65 B uncompressed keys (0x04 || X || Y), zeroed for failed items.  The call also uses
+ * pub65_out as working storage until it completes.
  * status: GSV_ST_OK / GSV_ST_INVALID_RECID (recid >= 4) / GSV_ST_RECOVER_FAILED.
  * addr20_out (optional, may be NULL): Keccak256(X || Y)[12:32] for OK items. */
 int gsv_ecrecover_batch(gsv_ctx *ctx, const uint8_t *msg32, const uint8_t *sig65, size_t n,

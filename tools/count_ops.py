@@ -2,7 +2,10 @@
 (geth-sharding_amd/csrc/opcount.cuh; built by `VSRCS="ecrecover ecverify ecdh bn256 bn_g1 notary collation"
 tools/build_variant.sh opcount -DGSV_OPCOUNT`), at the bench's batch sizes:
 
-    recovery       one k_ecrecover lane of the configs[1] batch (2^20 signatures)
+    recovery       one recovery of the configs[1] batch (2^20 signatures): its k_ecrecover lane plus its share
+                   of k_rinv_batch, which runs the safegcd and 3 (RINV_K - 1) scalar products once per RINV_K
+                   recoveries (both kernels count into ecrecover.hip's counters, read after the call);
+                   `python tools/count_ops.py recovery` prints this unit alone
     pairing_check  one 4-pair check of the configs[4] batch on one GPU (65,536 checks) and of the
                    per-rank batch at N = 8 (8,192 checks: another lane layout, §3.4 of DESIGN.md)
     notary_tx      one transaction of the configs[3] step (100 shards x 8,192 txs through k_notary_tx:
@@ -119,6 +122,10 @@ def main():
     c = per_unit(read("ecrecover"), n)
     c["mac_equiv"] = round(sum(W[k] * c.get(k, 0) for k in ("fe_mul", "fe_sqr", "sc_mul", "sc_sqr", "fe_dot", "fe_dot_ms")), 1)
     out["recovery"] = c
+    if sys.argv[1:] == ["recovery"]:
+        json.dump(out, sys.stdout, indent=1)
+        print()
+        return
     # ---- configs[4]: 4-pair checks, one GPU's batch and the 8-rank per-rank batch
     for name, nchk in (("pairing_check", 65536), ("pairing_check_8192", 8192)):
         pin = torch.empty((nchk, 768), dtype=torch.uint8, device=dev)
