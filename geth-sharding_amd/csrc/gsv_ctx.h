@@ -8,6 +8,7 @@
 //   gsv_ethash.hip   ethash: dataset items, hashimotoLight / Full, VerifySeal, Seal; the epochs' caches and datasets
 //   gsv_block_header.hip  types.Header hashes, CalcDifficulty, Ethash.VerifyHeaders: the launch chain around the seal
 //   gsv_receipt.hip  bloom9, CreateBloom and the receipt half of ValidateState: the launch chain around DeriveSha
+//   gsv_bloombits.hip  the bloombits generator, the bitset codec, the matcher and bloomFilter
 //   gsv_trie.hip     chunk root, DeriveSha, Proof of Custody, collation headers
 //   gsv_pairing.hip  BN254 pairing check
 //   gsv_notary.hip   notary validation, shard partition + RCCL all-gather
@@ -197,8 +198,8 @@ struct gsv_ctx {
     struct Pending { int kid; hipEvent_t a, b; };
     std::vector<Pending> pending;
     std::vector<hipEvent_t> free_events;
-    double total_ms[GSV_K_CREST] = {0};
-    long launches[GSV_K_CREST] = {0};
+    double total_ms[GSV_K_RIDGE] = {0};
+    long launches[GSV_K_RIDGE] = {0};
     std::mutex tmu;
     std::vector<hipEvent_t> open_ev;  // timer events opened by launch hooks
     hipStream_t cur_stream = nullptr;  // stream of the shape run in progress (launch hooks)

@@ -382,7 +382,7 @@ int gsv_ctx_set_pipeline_depth(gsv_ctx* c, int depth) {
 }
 
 int gsv_ctx_kernel_time(gsv_ctx* c, int kid, double* total_ms, long* launches) {
-    if (!c || kid < 0 || kid >= GSV_K_CREST) return GSV_E_INVALID_ARG;
+    if (!c || kid < 0 || kid >= GSV_K_RIDGE) return GSV_E_INVALID_ARG;
     drain_timing(c);
     if (total_ms) *total_ms = c->total_ms[kid];
     if (launches) *launches = c->launches[kid];
@@ -392,7 +392,7 @@ int gsv_ctx_kernel_time(gsv_ctx* c, int kid, double* total_ms, long* launches) {
 int gsv_ctx_reset_timing(gsv_ctx* c) {
     if (!c) return GSV_E_INVALID_ARG;
     drain_timing(c);
-    for (int i = 0; i < GSV_K_CREST; i++) {
+    for (int i = 0; i < GSV_K_RIDGE; i++) {
         c->total_ms[i] = 0;
         c->launches[i] = 0;
     }

@@ -212,6 +212,29 @@ hipError_t launch_receipt_check(const uint8_t* d_list_status, uint32_t n_lists, 
 // bloom9's three bit numbers per message: d_idx n x 3 uint16
 hipError_t launch_bloom9(const uint8_t* d_data, const uint64_t* d_off, uint32_t n, uint16_t* d_idx, hipStream_t st);
 
+// bloombits.hip: the section generator, the bitset codec, the matcher and bloomFilter (include/gsv.h "bloombits";
+// the bounds are bloombits_host.h's).  Byte arrays have any alignment; offsets and counts their natural one.
+hipError_t launch_bloombits_generate(const uint8_t* d_blooms, uint32_t n_sections, uint32_t S, uint8_t* d_bits,
+                                     hipStream_t st);
+hipError_t launch_bitset_compress(const uint8_t* d_in, uint32_t n, uint32_t L, uint8_t* d_slots, uint32_t* d_len,
+                                  hipStream_t st);
+hipError_t launch_bitset_decompress(const uint8_t* d_data, const uint64_t* d_off, uint32_t n, uint32_t L, uint8_t* d_out,
+                                    uint8_t* d_status, hipStream_t st);
+hipError_t launch_bloombits_match(const uint8_t* d_bits, uint32_t S, uint64_t first_section, uint32_t n_sections,
+                                  const uint16_t* d_clauses, uint32_t n_clauses, const uint32_t* d_rule_off,
+                                  uint32_t n_rules, const uint32_t* d_query_off, uint32_t n_queries,
+                                  const uint64_t* d_begin, const uint64_t* d_end, uint8_t* d_match, uint32_t* d_count,
+                                  hipStream_t st);
+hipError_t launch_bloombits_totals(const uint32_t* d_count, uint32_t n_sections, uint32_t n_queries,
+                                   uint64_t* d_block_off, hipStream_t st);
+hipError_t launch_bloombits_scan(uint64_t* d_block_off, uint32_t n_queries, hipStream_t st);
+hipError_t launch_bloombits_blocks(const uint8_t* d_match, const uint32_t* d_count, uint32_t S, uint64_t first_section,
+                                   uint32_t n_sections, uint32_t n_queries, const uint64_t* d_block_off,
+                                   uint64_t* d_blocks, uint64_t capacity, hipStream_t st);
+hipError_t launch_bloom_filter(const uint8_t* d_blooms, uint32_t n_blooms, const uint16_t* d_clauses, uint32_t n_clauses,
+                               const uint32_t* d_rule_off, uint32_t n_rules, const uint32_t* d_query_off,
+                               uint32_t n_queries, uint8_t* d_out, hipStream_t st);
+
 // collation.hip: CollationHeader.Hash() with ProposerSignature empty (k_header_hash alone: the hash the
 // proposer signs), no nil fields
 hipError_t launch_header_hash_unsigned(const uint8_t* d_sid32, const uint8_t* d_root32, const uint8_t* d_per32,

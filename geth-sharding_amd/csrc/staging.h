@@ -320,6 +320,62 @@ struct ReceiptStage {
           want_bloom(L.buf(n_lists * 256, has_bloom)), want_root(L.buf(n_lists * 32, has_root)),
           want_gas(L.buf<uint64_t>(n_lists * 8, has_gas)) {}
 };
+// gsv_bloombits_generate_batch: the sections' blooms in, the table out
+struct BloombitsGenerateStage {
+    B8 blooms, bits;
+    BloombitsGenerateStage(Layout& L, size_t bloom_bytes, size_t table_bytes)
+        : blooms(L.buf(bloom_bytes)), bits(L.buf(table_bytes)) {}
+};
+// gsv_bitset_compress_batch: n vectors of `len` bytes in; their slots and lengths out
+struct BitsetCompressStage {
+    B8 in, slots;
+    Buf<uint32_t> len;
+    BitsetCompressStage(Layout& L, size_t n, size_t len_)
+        : in(L.buf(n * len_)), slots(L.buf(n * len_)), len(L.buf<uint32_t>(n * 4)) {}
+};
+// gsv_bitset_decompress_batch: the packed inputs and their rebased table in; n rows of `len` bytes and a status out
+struct BitsetDecompressStage {
+    B8 data;
+    Buf<uint64_t> off;
+    B8 out, st;
+    BitsetDecompressStage(Layout& L, size_t bytes, size_t n, size_t len)
+        : data(L.buf(bytes + 8)), off(L.buf<uint64_t>((n + 1) * 8)), out(L.buf(n * len)), st(L.buf(n)) {}
+};
+// the filter system of gsv_bloombits_match_batch and gsv_bloom_filter_batch: the kept clauses' bytes and their table
+// (what bloom9 hashes), the three bit numbers of each, and the two tables of the rules that remain
+struct FilterStage {
+    B8 data;
+    Buf<uint64_t> off;
+    Buf<uint16_t> idx;
+    Buf<uint32_t> rule_off, query_off;
+    FilterStage(Layout& L, size_t bytes, size_t n_clauses, size_t n_rules, size_t n_queries)
+        : data(L.buf(bytes + 8)), off(L.buf<uint64_t>((n_clauses + 1) * 8)), idx(L.buf<uint16_t>(n_clauses * 6)),
+          rule_off(L.buf<uint32_t>((n_rules + 1) * 4)), query_off(L.buf<uint32_t>((n_queries + 1) * 4)) {}
+};
+// gsv_bloombits_match_batch: the filter, the table and the ranges in; the match bitsets and counts between the
+// launches; the scanned totals and the block numbers out
+struct BloombitsMatchStage {
+    FilterStage f;
+    B8 bits;
+    Buf<uint64_t> begin, end;
+    B8 match;
+    Buf<uint32_t> count;
+    Buf<uint64_t> block_off, blocks;
+    BloombitsMatchStage(Layout& L, size_t clause_bytes, size_t n_clauses, size_t n_rules, size_t n_queries,
+                        size_t table_bytes, size_t match_bytes, size_t pairs, size_t capacity)
+        : f(L, clause_bytes, n_clauses, n_rules, n_queries), bits(L.buf(table_bytes)),
+          begin(L.buf<uint64_t>(n_queries * 8)), end(L.buf<uint64_t>(n_queries * 8)), match(L.buf(match_bytes)),
+          count(L.buf<uint32_t>(pairs * 4)), block_off(L.buf<uint64_t>((n_queries + 1) * 8)),
+          blocks(L.buf<uint64_t>(capacity * 8)) {}
+};
+// gsv_bloom_filter_batch: the filter and the blooms in, a byte per (query, bloom) out
+struct BloomFilterStage {
+    FilterStage f;
+    B8 blooms, out;
+    BloomFilterStage(Layout& L, size_t clause_bytes, size_t n_clauses, size_t n_rules, size_t n_queries, size_t n_blooms)
+        : f(L, clause_bytes, n_clauses, n_rules, n_queries), blooms(L.buf(n_blooms * 256)),
+          out(L.buf(n_queries * n_blooms)) {}
+};
 
 }  // namespace api
 }  // namespace gsv

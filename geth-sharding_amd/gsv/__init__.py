@@ -1400,6 +1400,142 @@ def _receipts_check_dev(self, list_status_t, list_bloom_t, root_t, gas_used_t, w
                                              _tptr(want_gas_t), int(n_lists), _tptr(status_t), _sp(stream)))
 
 
+# ------------------------------------------------------------------ bloombits: generator, codec, matcher, bloomFilter
+def _bloombits_generate_batch(self, blooms, section_size: int) -> np.ndarray:
+    """The bit vectors of whole sections (gsv.h gsv_bloombits_generate_batch).  blooms: (n_sections * section_size,
+    256) bytes; returns (n_sections, 2048, section_size // 8) uint8."""
+    rows = np.ascontiguousarray(blooms, np.uint8).reshape(-1, 256)
+    s = int(section_size)
+    if s <= 0 or rows.shape[0] % s:
+        raise ValueError("bloombits: a whole number of sections of section_size blooms")
+    n = rows.shape[0] // s
+    out = np.zeros((n, _lib.BLOOM_BITS, s // 8), np.uint8)
+    check(_lib.load().gsv_bloombits_generate_batch(self._h, _ptr(rows), n, s, _ptr(out)))
+    return out
+
+
+def _bloombits_generate_dev(self, blooms_t, n_sections: int, section_size: int, bits_t, stream=None):
+    """blooms_t: n_sections * section_size rows of 256 bytes; bits_t: the table; torch uint8 CUDA tensors"""
+    check(_lib.load().gsv_bloombits_generate_dev(self._h, _tptr(blooms_t), int(n_sections), int(section_size),
+                                                 _tptr(bits_t), _sp(stream)))
+
+
+def _bitset_compress_batch(self, vectors):
+    """bitutil.CompressBytes of n vectors of one length (gsv.h gsv_bitset_compress_batch): a list of bytes"""
+    rows = np.ascontiguousarray(vectors, np.uint8)
+    rows = rows.reshape(rows.shape[0], -1) if rows.ndim else rows.reshape(0, 1)
+    n, length = rows.shape
+    out = np.zeros(max(n * length, 1), np.uint8)
+    off = np.zeros(n + 1, np.uint64)
+    check(_lib.load().gsv_bitset_compress_batch(self._h, _ptr(rows), n, length, _ptr(out), _ptr(off)))
+    return [out[int(off[i]):int(off[i + 1])].tobytes() for i in range(n)]
+
+
+def _bitset_compress_batch_dev(self, in_t, n: int, length: int, slots_t, len_t, stream=None):
+    """in_t, slots_t: n rows of `length` bytes; len_t: n int32; torch CUDA tensors"""
+    check(_lib.load().gsv_bitset_compress_batch_dev(self._h, _tptr(in_t), int(n), int(length), _tptr(slots_t),
+                                                    _tptr(len_t), _sp(stream)))
+
+
+def _bitset_decompress_batch(self, items, target: int):
+    """bitutil.DecompressBytes(item, target) of each byte string (gsv.h gsv_bitset_decompress_batch): (rows
+    (n, target) uint8, status (n,) uint8)"""
+    items = [bytes(x) for x in items]
+    n = len(items)
+    flat, off = _pack(items)
+    out = np.zeros((n, int(target)), np.uint8)
+    st = np.zeros(n, np.uint8)
+    check(_lib.load().gsv_bitset_decompress_batch(self._h, _ptr(flat), _ptr(off), n, int(target), _ptr(out), _ptr(st)))
+    return out, st
+
+
+def _bitset_decompress_batch_dev(self, data_t, off_t, n: int, length: int, out_t, status_t, stream=None):
+    check(_lib.load().gsv_bitset_decompress_batch_dev(self._h, _tptr(data_t), _tptr(off_t), int(n), int(length),
+                                                      _tptr(out_t), _tptr(status_t), _sp(stream)))
+
+
+def _filter_tables(queries):
+    """queries: per query a list of rules, a rule a list of clauses (bytes, or None for a nil clause), or None for a nil
+    rule -> (flat, clause_off, nil, rule_off, query_off) as the host forms take the filter"""
+    clauses, nil, rule_off, query_off = [], [], [0], [0]
+    for rules in queries:
+        for rule in rules or []:
+            for cl in rule or []:
+                nil.append(1 if cl is None else 0)
+                clauses.append(b"" if cl is None else bytes(cl))
+            rule_off.append(len(clauses))
+        query_off.append(len(rule_off) - 1)
+    flat, clause_off = _pack(clauses)
+    return (flat, clause_off, np.array(nil + [0], np.uint8), np.array(rule_off, np.uint64),
+            np.array(query_off, np.uint64))
+
+
+def _bloombits_match_batch(self, table, section_size: int, first_section: int, queries, begin, end, capacity=None):
+    """Many queries over one table (gsv.h gsv_bloombits_match_batch).  table: (n_sections, 2048, section_size // 8)
+    uint8; queries as _filter_tables takes them; begin / end: one block range per query, both ends included.
+    Returns a list of uint64 arrays, one per query.  capacity None: the call is repeated with the true total when
+    the first guess was short."""
+    bits = np.ascontiguousarray(table, np.uint8)
+    s = int(section_size)
+    n_sections = bits.size // (_lib.BLOOM_BITS * (s // 8)) if s >= 8 else 0
+    nq = len(queries)
+    flat, coff, nil, roff, qoff = _filter_tables(queries)
+    b = np.ascontiguousarray(begin, np.uint64).reshape(-1)
+    e = np.ascontiguousarray(end, np.uint64).reshape(-1)
+    if b.shape[0] != nq or e.shape[0] != nq:
+        raise ValueError("bloombits: one [begin, end] per query")
+    cap = 4096 * max(nq, 1) if capacity is None else int(capacity)
+    while True:
+        block_off = np.zeros(nq + 1, np.uint64)
+        blocks = np.zeros(max(cap, 1), np.uint64)
+        check(_lib.load().gsv_bloombits_match_batch(self._h, _ptr(bits), s, int(first_section), n_sections, _ptr(flat),
+                                                    _ptr(coff), _ptr(nil), _ptr(roff), _ptr(qoff), nq, _ptr(b), _ptr(e),
+                                                    _ptr(block_off), _ptr(blocks), cap))
+        total = int(block_off[-1])
+        if total <= cap or capacity is not None:
+            break
+        cap = total
+    return [blocks[int(block_off[q]):min(int(block_off[q + 1]), cap)].copy() for q in range(nq)]
+
+
+def _bloombits_match_dev(self, bits_t, section_size: int, first_section: int, n_sections: int, clauses_t, n_clauses: int,
+                         rule_off_t, n_rules: int, query_off_t, n_queries: int, begin_t, end_t, match_t, count_t,
+                         stream=None):
+    """The match bitsets and counts over torch CUDA tensors (gsv.h gsv_bloombits_match_dev): clauses_t (n, 3) int16 as
+    bloom9_batch_dev writes them, the two tables int32, the ranges int64"""
+    check(_lib.load().gsv_bloombits_match_dev(self._h, _tptr(bits_t), int(section_size), int(first_section),
+                                              int(n_sections), _tptr(clauses_t), int(n_clauses), _tptr(rule_off_t),
+                                              int(n_rules), _tptr(query_off_t), int(n_queries), _tptr(begin_t),
+                                              _tptr(end_t), _tptr(match_t), _tptr(count_t), _sp(stream)))
+
+
+def _bloombits_blocks_dev(self, match_t, count_t, section_size: int, first_section: int, n_sections: int, n_queries: int,
+                          block_off_t, blocks_t, capacity: int, stream=None):
+    """The match bitsets as block numbers (gsv.h gsv_bloombits_blocks_dev): block_off_t n_queries + 1 int64, blocks_t
+    `capacity` int64"""
+    check(_lib.load().gsv_bloombits_blocks_dev(self._h, _tptr(match_t), _tptr(count_t), int(section_size),
+                                               int(first_section), int(n_sections), int(n_queries), _tptr(block_off_t),
+                                               _tptr(blocks_t), int(capacity), _sp(stream)))
+
+
+def _bloom_filter_batch(self, blooms, queries) -> np.ndarray:
+    """bloomFilter of every bloom under every query (gsv.h gsv_bloom_filter_batch): (n_queries, n_blooms) bool"""
+    rows = np.ascontiguousarray(blooms, np.uint8).reshape(-1, 256)
+    nq = len(queries)
+    flat, coff, nil, roff, qoff = _filter_tables(queries)
+    out = np.zeros((nq, rows.shape[0]), np.uint8)
+    check(_lib.load().gsv_bloom_filter_batch(self._h, _ptr(rows), rows.shape[0], _ptr(flat), _ptr(coff), _ptr(nil),
+                                             _ptr(roff), _ptr(qoff), nq, _ptr(out)))
+    return out.astype(bool)
+
+
+def _bloom_filter_dev(self, blooms_t, n_blooms: int, clauses_t, n_clauses: int, rule_off_t, n_rules: int, query_off_t,
+                      n_queries: int, out_t, stream=None):
+    check(_lib.load().gsv_bloom_filter_dev(self._h, _tptr(blooms_t), int(n_blooms), _tptr(clauses_t), int(n_clauses),
+                                           _tptr(rule_off_t), int(n_rules), _tptr(query_off_t), int(n_queries),
+                                           _tptr(out_t), _sp(stream)))
+
+
 def _arena_read(self, off, n):
     """Test hook (gsv.h gsv_ctx_arena_read): n bytes of the staging arena from `off`, as they are now."""
     out = np.zeros(n, np.uint8)
@@ -1456,6 +1592,17 @@ Context.bloom9_batch_dev = _bloom9_batch_dev
 Context.receipts_verify_batch = _receipts_verify_batch
 Context.receipts_bloom_dev = _receipts_bloom_dev
 Context.receipts_check_dev = _receipts_check_dev
+Context.bloombits_generate_batch = _bloombits_generate_batch
+Context.bloombits_generate_dev = _bloombits_generate_dev
+Context.bitset_compress_batch = _bitset_compress_batch
+Context.bitset_compress_batch_dev = _bitset_compress_batch_dev
+Context.bitset_decompress_batch = _bitset_decompress_batch
+Context.bitset_decompress_batch_dev = _bitset_decompress_batch_dev
+Context.bloombits_match_batch = _bloombits_match_batch
+Context.bloombits_match_dev = _bloombits_match_dev
+Context.bloombits_blocks_dev = _bloombits_blocks_dev
+Context.bloom_filter_batch = _bloom_filter_batch
+Context.bloom_filter_dev = _bloom_filter_dev
 Context.modexp_batch = _modexp_batch
 Context.modexp_batch_dev = _modexp_batch_dev
 Context._arena_read = _arena_read

@@ -51,6 +51,10 @@ ST_RECEIPT_STATUS = 33
 ST_GAS_USED_MISMATCH = 34
 ST_INVALID_BLOOM = 35
 ST_INVALID_RECEIPT_ROOT = 36
+ST_BITSET_MISSING_DATA = 37
+ST_BITSET_UNREFERENCED_DATA = 38
+ST_BITSET_EXCEEDED_TARGET = 39
+ST_BITSET_ZERO_CONTENT = 40
 
 # a short text per per-item status: the reference's error string where it has one (include/gsv.h names
 # the sources)
@@ -92,6 +96,10 @@ STATUS_STRINGS = {
     ST_GAS_USED_MISMATCH: "invalid gas used",
     ST_INVALID_BLOOM: "invalid bloom",
     ST_INVALID_RECEIPT_ROOT: "invalid receipt root hash",
+    ST_BITSET_MISSING_DATA: "missing bytes on input",
+    ST_BITSET_UNREFERENCED_DATA: "extra bytes on input",
+    ST_BITSET_EXCEEDED_TARGET: "target data size exceeded",
+    ST_BITSET_ZERO_CONTENT: "zero byte in input content",
 }
 
 SIGNER_EIP155 = 0
@@ -136,10 +144,23 @@ K_RECEIPT_BLOOM = 27
 K_RECEIPT_LISTS = 28
 K_RECEIPT_CHECK = 29
 K_BLOOM9 = 30
-K_CREST = 31  # GSV_K_CREST: gsv_ctx_kernel_time takes every id below it
+K_CREST = 31  # GSV_K_CREST: pinned; the ids behind it follow
+K_BLOOMBITS_GENERATE = 31
+K_BITSET_COMPRESS = 32
+K_BITSET_DECOMPRESS = 33
+K_BLOOMBITS_MATCH = 34
+K_BLOOMBITS_TOTALS = 35
+K_BLOOMBITS_SCAN = 36
+K_BLOOMBITS_BLOCKS = 37
+K_BLOOM_FILTER = 38
+K_RIDGE = 39  # GSV_K_RIDGE: gsv_ctx_kernel_time takes every id below it
 
 ETHASH_MAX_CACHES = 3  # GSV_ETHASH_MAX_CACHES: epoch caches a context keeps for the ethash host forms
 ETHASH_MAX_DATASETS = 2  # GSV_ETHASH_MAX_DATASETS: epoch datasets a context keeps for the full and seal forms
+
+BLOOMBITS_MAX_SECTION = 32768  # GSV_BLOOMBITS_MAX_SECTION: blooms of one section, a multiple of 8 from 8 up
+BLOOM_BITS = 2048  # GSV_BLOOM_BITS: bit vectors of a section
+BITSET_MAX_LEN = 4096  # GSV_BITSET_MAX_LEN: the longest vector the bitset codec takes
 
 MODEXP_MAX_LEN = 1024  # GSV_MODEXP_MAX_LEN: the cap on baseLen, expLen and modLen of the modexp precompile
 
@@ -287,6 +308,19 @@ SIGNATURES = [
     ("gsv_receipts_bloom_dev", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("gsv_receipts_check_dev", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     ("gsv_receipts_verify_batch", ctypes.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("gsv_bloombits_generate_batch", ctypes.c_int, [_vp, _vp, _sz, ctypes.c_uint32, _vp]),
+    ("gsv_bloombits_generate_dev", ctypes.c_int, [_vp, _vp, _sz, ctypes.c_uint32, _vp, _vp]),
+    ("gsv_bitset_compress_batch", ctypes.c_int, [_vp, _vp, _sz, ctypes.c_uint32, _vp, _vp]),
+    ("gsv_bitset_compress_batch_dev", ctypes.c_int, [_vp, _vp, _sz, ctypes.c_uint32, _vp, _vp, _vp]),
+    ("gsv_bitset_decompress_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, ctypes.c_uint32, _vp, _vp]),
+    ("gsv_bitset_decompress_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _sz, ctypes.c_uint32, _vp, _vp, _vp]),
+    ("gsv_bloombits_match_dev", ctypes.c_int, [_vp, _vp, ctypes.c_uint32, _u64, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp,
+                                               _vp, _vp, _vp, _vp]),
+    ("gsv_bloombits_blocks_dev", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint32, _u64, _sz, _sz, _vp, _vp, _u64, _vp]),
+    ("gsv_bloombits_match_batch", ctypes.c_int, [_vp, _vp, ctypes.c_uint32, _u64, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
+                                                 _vp, _vp, _vp, _u64]),
+    ("gsv_bloom_filter_dev", ctypes.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
+    ("gsv_bloom_filter_batch", ctypes.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     ("gsv_chunk_root_prepare", ctypes.c_int, [_vp, _vp, _sz]),
     ("gsv_bn256_pairing_prepare", ctypes.c_int, [_vp, _vp, _sz]),
     ("gsv_notary_prepare", ctypes.c_int, [_vp, _vp, _sz, _vp, _sz, ctypes.c_int, ctypes.c_uint32]),

@@ -76,6 +76,12 @@
  *   gsv_receipts_verify_batch  <- types.CreateBloom (bloom9.go:94-113), the receipt root and the three receipt
  *                                 compares of BlockValidator.ValidateState (core/block_validator.go:80-95) over
  *                                 RLP-encoded receipts (core/types/receipt.go:67-128)
+ *   gsv_bloombits_generate_batch <- bloombits.Generator (core/bloombits/generator.go:52-87) over whole sections,
+ *                                 as BloomIndexer.Process / Commit feed it (eth/bloombits.go:126-141)
+ *   gsv_bitset_compress_batch  <- bitutil.CompressBytes / DecompressBytes (common/bitutil/compress.go:60-170)
+ *   gsv_bloombits_match_batch  <- bloombits.NewMatcher and what a Matcher session computes
+ *                                 (core/bloombits/matcher.go:92-131, :182-211, :337-366)
+ *   gsv_bloom_filter_batch     <- bloomFilter (eth/filters/filter.go:278-305) after filters.New's flattening (:62-93)
  *
  * Conventions
  *   - Return value: GSV_SUCCESS (0) or a negative GSV_E_* API/HIP error. A bad ITEM never fails
@@ -163,6 +169,11 @@ extern "C" {
 #define GSV_ST_GAS_USED_MISMATCH 34    /* "invalid gas used"           core/block_validator.go:82-84 */
 #define GSV_ST_INVALID_BLOOM 35        /* "invalid bloom"              core/block_validator.go:87-90 */
 #define GSV_ST_INVALID_RECEIPT_ROOT 36 /* "invalid receipt root hash"  core/block_validator.go:92-95 */
+/* bitset decompression (gsv_bitset_decompress_batch): common/bitutil/compress.go:21-37 */
+#define GSV_ST_BITSET_MISSING_DATA 37      /* errMissingData       "missing bytes on input"      :24 */
+#define GSV_ST_BITSET_UNREFERENCED_DATA 38 /* errUnreferencedData  "extra bytes on input"        :28 */
+#define GSV_ST_BITSET_EXCEEDED_TARGET 39   /* errExceededTarget    "target data size exceeded"   :32 */
+#define GSV_ST_BITSET_ZERO_CONTENT 40      /* errZeroContent       "zero byte in input content"  :36 */
 
 /* signer kinds for gsv_tx_sender_batch and gsv_tx_sign_batch (core/types/transaction_signing.go) */
 #define GSV_SIGNER_EIP155 0
@@ -245,6 +256,17 @@ int gsv_ctx_set_timing(gsv_ctx *ctx, int enable);
 #define GSV_K_RECEIPT_CHECK 29 /* receipts: gas used, bloom and root against the header's: one launch per call */
 #define GSV_K_BLOOM9 30        /* bloom9 over byte strings: one launch per call */
 #define GSV_K_CREST 31
+/* Ids added behind GSV_K_CREST (pinned like the eight before it); gsv_ctx_kernel_time takes every id below
+ * GSV_K_RIDGE. */
+#define GSV_K_BLOOMBITS_GENERATE 31 /* bloombits: the section transposition, one launch per call */
+#define GSV_K_BITSET_COMPRESS 32    /* bitutil.CompressBytes over n vectors: one launch per call */
+#define GSV_K_BITSET_DECOMPRESS 33  /* bitutil.DecompressBytes over n vectors: one launch per call */
+#define GSV_K_BLOOMBITS_MATCH 34    /* bloombits: the match bitsets and counts, one launch per call */
+#define GSV_K_BLOOMBITS_TOTALS 35   /* bloombits blocks: each query's total, one launch per call */
+#define GSV_K_BLOOMBITS_SCAN 36     /* bloombits blocks: the totals scanned into block_off, one launch per call */
+#define GSV_K_BLOOMBITS_BLOCKS 37   /* bloombits blocks: the block numbers, one launch per call */
+#define GSV_K_BLOOM_FILTER 38       /* bloomFilter over plain blooms: one launch per call */
+#define GSV_K_RIDGE 39
 /* total milliseconds and launch count accumulated for kernel `kid` since the last reset */
 int gsv_ctx_kernel_time(gsv_ctx *ctx, int kid, double *total_ms, long *launches);
 int gsv_ctx_reset_timing(gsv_ctx *ctx);
@@ -1050,6 +1072,104 @@ int gsv_receipts_verify_batch(gsv_ctx *ctx, const uint8_t *vals, const uint64_t 
                               size_t n_lists, const uint8_t *want_bloom256, const uint8_t *want_root32,
                               const uint64_t *want_gas_used, uint8_t *receipt_status, uint8_t *list_bloom256,
                               uint8_t *root32, uint64_t *gas_used, uint8_t *status);
+
+/* ---- bloombits: section generator, bitset codec, matcher, bloomFilter ----
+ * Mirrors core/bloombits (generator.go, matcher.go), the codec of common/bitutil (compress.go) and bloomFilter
+ * (eth/filters/filter.go:278-305).  Results are byte for byte the reference's.
+ *
+ * Numbering.  Bloom bit b (0 .. 2047) of a 256-byte bloom is byte 255 - b / 8 under mask 1 << (b % 8)
+ * (generator.go:64-70): the numbers gsv_bloom9_batch returns.  A section of S blooms, S % 8 == 0 (:40), becomes
+ * 2,048 bit vectors of S / 8 bytes; block j of the section is byte j / 8 of a vector under mask 1 << (7 - j % 8)
+ * (:61-62).  The table of n_sections sections is dense: bits[(section * 2048 + bit) * (S / 8) + byte].
+ * OURS: 8 <= S <= 32,768 (GSV_BLOOMBITS_MAX_SECTION; the reference's own benchmark stops there,
+ * eth/filters/bench_test.go:60) and S % 8 == 0; anything else is GSV_E_INVALID_ARG.  OURS: at most 2^20 sections and
+ * 2^20 queries, rules and clauses a call, and at most 2^24 (query, section) pairs.
+ *
+ * Every _dev form takes device arrays and only enqueues on `stream` (NULL = the context stream): no allocation, no
+ * synchronisation, no prepare call, capturable.  A NULL context or required array, a misaligned table of offsets
+ * or counts, or a size past the bounds above is GSV_E_INVALID_ARG before any HIP call.  A call over no items
+ * (n_sections, n, n_queries or n_blooms of 0) is success and enqueues nothing.
+ *
+ * 1. Generator (generator.go:52-87: AddBloom over a whole section, then every Bitset).  blooms: n_sections x S rows
+ *    of 256 bytes, any alignment; bits: the table above, any alignment.  One launch (GSV_K_BLOOMBITS_GENERATE). */
+#define GSV_BLOOMBITS_MAX_SECTION 32768
+#define GSV_BLOOM_BITS 2048
+int gsv_bloombits_generate_batch(gsv_ctx *ctx, const uint8_t *blooms256, size_t n_sections, uint32_t section_size,
+                                 uint8_t *bits_out);
+int gsv_bloombits_generate_dev(gsv_ctx *ctx, const uint8_t *d_blooms256, size_t n_sections, uint32_t section_size,
+                               uint8_t *d_bits, void *stream);
+/* 2. Codec over n vectors of one length L each, 1 <= L <= GSV_BITSET_MAX_LEN, n < 2^31.
+ *    Compress = CompressBytes (compress.go:60-67) around bitsetEncodeBytes (:71-97): vector i = d_in[i L .. i L + L);
+ *    its result lies in slot i = d_slots[i L ..) with d_len[i] (4-byte aligned) bytes: 0 = all zero (:93-95, :78-80),
+ *    L = stored raw (:61-66: the encoding was not shorter), else the recursive encoding.  The encoding of a dense
+ *    vector is longer than L, so the kernel settles the length before it writes: no byte of a slot behind d_len[i]
+ *    and no byte outside the slots is written.  One launch (GSV_K_BITSET_COMPRESS).  The host form returns the
+ *    packed concatenation: out_off[n + 1] (out_off[0] = 0) and out, which must hold n * L bytes.
+ *    Decompress = DecompressBytes(data, L) (:102-112): input i = d_data[d_off[i] .. d_off[i + 1]) (n + 1 offsets,
+ *    8-byte aligned, any start), output row i = d_out[i L ..), d_status[i]: GSV_ST_OK or the FIRST error the
+ *    reference's recursion meets: a longer input than L is GSV_ST_BITSET_EXCEEDED_TARGET (:103-105), one of L bytes
+ *    is copied (:106-110); else bitsetDecodePartialBytes (:130-170) innermost level first (:148-151), inside a level
+ *    per set bit in order: GSV_ST_BITSET_MISSING_DATA (:155-157), GSV_ST_BITSET_EXCEEDED_TARGET (:158-160),
+ *    GSV_ST_BITSET_ZERO_CONTENT (:162-164); last GSV_ST_BITSET_UNREFERENCED_DATA (:120-122).  OURS: an entry of the
+ *    table that steps backwards is GSV_ST_BITSET_MISSING_DATA unread.  A failed vector's output row is zero.  One
+ *    launch (GSV_K_BITSET_DECOMPRESS).  The host form checks its table (ascending, else GSV_E_INVALID_ARG). */
+#define GSV_BITSET_MAX_LEN 4096
+int gsv_bitset_compress_batch(gsv_ctx *ctx, const uint8_t *in, size_t n, uint32_t len, uint8_t *out,
+                              uint64_t *out_off);
+int gsv_bitset_compress_batch_dev(gsv_ctx *ctx, const uint8_t *d_in, size_t n, uint32_t len, uint8_t *d_slots,
+                                  uint32_t *d_len, void *stream);
+int gsv_bitset_decompress_batch(gsv_ctx *ctx, const uint8_t *data, const uint64_t *off, size_t n, uint32_t len,
+                                uint8_t *out, uint8_t *status);
+int gsv_bitset_decompress_batch_dev(gsv_ctx *ctx, const uint8_t *d_data, const uint64_t *d_off, size_t n, uint32_t len,
+                                    uint8_t *d_out, uint8_t *d_status, void *stream);
+/* 3. Matcher.  The filter system of many queries over one table, as NewMatcher leaves it in Matcher.filters
+ *    (matcher.go:105-122): query q holds rules [d_query_off[q], d_query_off[q + 1]), rule r holds clauses
+ *    [d_rule_off[r], d_rule_off[r + 1]) (both uint32, 4-byte aligned, n_queries + 1 and n_rules + 1 entries), clause c
+ *    is the three uint16 bit numbers d_clauses[3 c ..) (2-byte aligned), each masked to 11 bits: the layout
+ *    gsv_bloom9_batch_dev writes.  An entry past n_rules / n_clauses is clamped to it, so no table is read past its
+ *    end.  d_begin / d_end (8-byte aligned): the query's block range, both ends included (matcher.go:147, :182-192).
+ *    d_bits holds sections [first_section, first_section + n_sections) of section_size blocks.
+ *    Per query and section: all ones (matcher.go:238); per rule the OR over its clauses of the AND of the clause's
+ *    three rows (:337-359), ANDed over the rules (:364-366); then the blocks outside [begin, end] cleared (:182-192).
+ *    A query with no rules matches every block of its range (TestWildcardMatcher); a rule with no clauses matches
+ *    none (:361-363; NewMatcher drops such a rule, and so do the host forms).  OURS: blocks outside the table are not
+ *    reported (the reference would wait for a retrieval).
+ *    match:  one launch (GSV_K_BLOOMBITS_MATCH).  d_match: n_queries x n_sections x S / 8 bytes, any alignment;
+ *            d_count (4-byte aligned): the set bits of each (query, section).
+ *    blocks: three launches (GSV_K_BLOOMBITS_TOTALS, _SCAN, _BLOCKS).  d_block_off (8-byte aligned, n_queries + 1):
+ *            the scan of the queries' totals, d_block_off[0] = 0; query q's block numbers, ascending, are
+ *            d_blocks[d_block_off[q] .. d_block_off[q + 1]) (8-byte aligned, `capacity` entries).  A number whose
+ *            place is at or past `capacity` is not written; d_block_off holds the true totals all the same, so the
+ *            caller sees the shortfall and calls again.
+ *    Host form: the filter as NewMatcher takes it.  Clause c = clause_data[clause_off[c] .. clause_off[c + 1]) with
+ *    clause_nil[c] != 0 for a nil clause (an empty clause that is not nil is hashed, a nil one is not; clause_nil
+ *    NULL = none is nil); rule_off / query_off as above but uint64 on the host.  It drops a rule with no clauses and
+ *    a rule with a nil clause (matcher.go:105-122), runs gsv_bloom9_batch_dev over the clauses that remain, then
+ *    match, then blocks.  block_off_out: n_queries + 1; blocks_out: `capacity` entries, filled as by blocks_dev. */
+int gsv_bloombits_match_dev(gsv_ctx *ctx, const uint8_t *d_bits, uint32_t section_size, uint64_t first_section,
+                            size_t n_sections, const uint16_t *d_clauses, size_t n_clauses, const uint32_t *d_rule_off,
+                            size_t n_rules, const uint32_t *d_query_off, size_t n_queries, const uint64_t *d_begin,
+                            const uint64_t *d_end, uint8_t *d_match, uint32_t *d_count, void *stream);
+int gsv_bloombits_blocks_dev(gsv_ctx *ctx, const uint8_t *d_match, const uint32_t *d_count, uint32_t section_size,
+                             uint64_t first_section, size_t n_sections, size_t n_queries, uint64_t *d_block_off,
+                             uint64_t *d_blocks, uint64_t capacity, void *stream);
+int gsv_bloombits_match_batch(gsv_ctx *ctx, const uint8_t *bits, uint32_t section_size, uint64_t first_section,
+                              size_t n_sections, const uint8_t *clause_data, const uint64_t *clause_off,
+                              const uint8_t *clause_nil, const uint64_t *rule_off, const uint64_t *query_off,
+                              size_t n_queries, const uint64_t *begin, const uint64_t *end, uint64_t *block_off_out,
+                              uint64_t *blocks_out, uint64_t capacity);
+/* 4. bloomFilter (eth/filters/filter.go:278-305) over n_blooms blooms of 256 bytes (any alignment), the queries in
+ *    the matcher's layout (their ranges play no part): d_out[q * n_blooms + k] = 1 when bloom k passes query q, else
+ *    0.  The rule evaluation is the matcher's; the bit test reads a bloom byte (BloomLookup, core/types/bloom9.go:131-
+ *    136) where the matcher reads a row.  One launch (GSV_K_BLOOM_FILTER).  The host form takes the filter as
+ *    gsv_bloombits_match_batch does and drops the same rules: filters.New (:62-93) never makes a nil clause, and a
+ *    rule without clauses is bloomFilter's wildcard (:293). */
+int gsv_bloom_filter_dev(gsv_ctx *ctx, const uint8_t *d_blooms256, size_t n_blooms, const uint16_t *d_clauses,
+                         size_t n_clauses, const uint32_t *d_rule_off, size_t n_rules, const uint32_t *d_query_off,
+                         size_t n_queries, uint8_t *d_out, void *stream);
+int gsv_bloom_filter_batch(gsv_ctx *ctx, const uint8_t *blooms256, size_t n_blooms, const uint8_t *clause_data,
+                           const uint64_t *clause_off, const uint8_t *clause_nil, const uint64_t *rule_off,
+                           const uint64_t *query_off, size_t n_queries, uint8_t *out);
 
 /* ---- Proof of Custody (sharding/collation.go:124-136) ----
  * poc32_out[i] = DeriveSha(Chunks(salt||b0||salt||b1||...)) over body i = bodies[off[i] .. off[i+1])
