@@ -145,14 +145,20 @@ def test_tx_sender_batch_golden(ctx, oracle):
         assert st[i] == s and (s != 0 or bytes(addr[i]) == a)
 
 
-def _signed_tx(oracle, key, nonce, data, chain_id, eip155=True, want_zero=None):
-    """An EIP-155 (or unprotected Homestead) transaction signed with `key`; want_zero = "r" / "s" retries
-    the signing nonce until that value's top byte is zero (a 31-byte or shorter RLP string)."""
+def _sighash_preimage(oracle, nonce, data, chain_id, eip155=True):
+    """(the six fields' RLP, the sighash preimage) of _signed_tx's transaction"""
     to = bytes(range(1, 21))
     fields = (oracle.rlp_uint(nonce) + oracle.rlp_uint(20 * 10 ** 9) + oracle.rlp_uint(21000 + len(data)) +
               oracle.rlp_string(to) + oracle.rlp_uint(10 ** 18 + nonce) + oracle.rlp_string(data))
     pre = fields + (oracle.rlp_uint(chain_id) + b"\x80\x80" if eip155 else b"")
-    h = oracle.keccak256(oracle.rlp_list(pre))
+    return fields, oracle.rlp_list(pre)
+
+
+def _signed_tx(oracle, key, nonce, data, chain_id, eip155=True, want_zero=None):
+    """An EIP-155 (or unprotected Homestead) transaction signed with `key`; want_zero = "r" / "s" retries
+    the signing nonce until that value's top byte is zero (a 31-byte or shorter RLP string)."""
+    fields, preimage = _sighash_preimage(oracle, nonce, data, chain_id, eip155)
+    h = oracle.keccak256(preimage)
     for k in range(1, 5000):
         sig = oracle.secp_sign(h, key, k.to_bytes(32, "big"))
         if want_zero is None or sig[0 if want_zero == "r" else 32] == 0:
@@ -190,3 +196,50 @@ def test_notary_preimage_shapes(ctx, oracle, chain_id):
     assert ntx[0] == len(txs)
     assert (status[0, :len(txs)] == ST_OK).all(), status[0, :len(txs)]
     assert all(bytes(senders[0, t]) == addr for t in range(len(txs)))
+
+
+RATE_BLOCK_EDGES = tuple(136 * k + d for k in (1, 2, 3) for d in range(-2, 3))  # 134...138, 270...274, 406...410
+
+
+def _list_header(enc: bytes) -> int:
+    return 1 if enc[0] < 0xf8 else 1 + enc[0] - 0xf7
+
+
+@pytest.mark.parametrize("chain_id", [1, 2 ** 63 + 5])
+def test_notary_preimage_rate_block_edges(ctx, oracle, chain_id):
+    """k_notary_tx absorbs the sighash preimage from the blob's chunks without materialising it; the padding
+    goes by the preimage's length, not the data's.  For every preimage length T within 2 of one, two and
+    three Keccak rate blocks (T = 136 k: an empty final block; 136 k - 1: 0x01 and 0x80 in one byte), EIP-155
+    and unprotected, the data length that gives it is searched on the measured preimage.  A length that no
+    data gives is asserted to be the one the list header's own growth steps over.  Statuses and senders
+    against the oracle's types.Sender and the signing key's address."""
+    key = bytes.fromhex("4c0883a69102937d6231471b5dbb6204fe5129617082792ae468d01a3f362318")
+    addr = oracle.keccak256(oracle.secp_pubkey(key)[1:])[12:]
+    rng = random.Random(136 + chain_id % 1000)
+    txs, reached = [], []
+    for eip155 in (True, False):
+        unreachable = []
+        for T in RATE_BLOCK_EDGES:
+            nonce = len(txs)
+
+            def pre(n):
+                return _sighash_preimage(oracle, nonce, bytes(n), chain_id, eip155)[1]
+            n = next((n for n in range(2, T + 1) if len(pre(n)) == T), None)
+            if n is None:
+                lo = max(n for n in range(2, T + 1) if len(pre(n)) < T)
+                a, b = pre(lo), pre(lo + 1)
+                assert len(a) == T - 1 and len(b) == T + 1 and _list_header(b) == _list_header(a) + 1, (eip155, T)
+                unreachable.append(T)
+                continue
+            data = bytes(rng.getrandbits(8) for _ in range(n))
+            assert len(_sighash_preimage(oracle, nonce, data, chain_id, eip155)[1]) == T
+            txs.append(_signed_tx(oracle, key, nonce, data, chain_id, eip155=eip155))
+            reached.append((eip155, T))
+        assert len(unreachable) <= 2, (eip155, unreachable)
+    print("preimage lengths:", reached)
+    assert 26 <= len(txs) <= 64
+    body = oracle.blob_serialize(txs)
+    _, ntx, _, senders, status = _check(ctx, oracle, [body], chain_id, 0, 64)
+    assert ntx[0] == len(txs)
+    bad = [reached[t] for t in range(len(txs)) if status[0, t] != ST_OK or bytes(senders[0, t]) != addr]
+    assert not bad, bad
