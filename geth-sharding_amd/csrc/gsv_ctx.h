@@ -9,6 +9,7 @@
 //   gsv_block_header.hip  types.Header hashes, CalcDifficulty, Ethash.VerifyHeaders: the launch chain around the seal
 //   gsv_receipt.hip  bloom9, CreateBloom and the receipt half of ValidateState: the launch chain around DeriveSha
 //   gsv_bloombits.hip  the bloombits generator, the bitset codec, the matcher and bloomFilter
+//   gsv_clique.hip   clique's voting snapshot and fold behind opaque handles: host only, it uses nothing of this header
 //   gsv_trie.hip     chunk root, DeriveSha, Proof of Custody, collation headers
 //   gsv_pairing.hip  BN254 pairing check
 //   gsv_notary.hip   notary validation, shard partition + RCCL all-gather

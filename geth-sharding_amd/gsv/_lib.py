@@ -55,6 +55,19 @@ ST_BITSET_MISSING_DATA = 37
 ST_BITSET_UNREFERENCED_DATA = 38
 ST_BITSET_EXCEEDED_TARGET = 39
 ST_BITSET_ZERO_CONTENT = 40
+ST_CLIQUE_CHECKPOINT_BENEFICIARY = 41
+ST_CLIQUE_INVALID_VOTE = 42
+ST_CLIQUE_CHECKPOINT_VOTE = 43
+ST_CLIQUE_MISSING_VANITY = 44
+ST_CLIQUE_MISSING_SIGNATURE = 45
+ST_CLIQUE_EXTRA_SIGNERS = 46
+ST_CLIQUE_CHECKPOINT_SIGNERS = 47
+ST_CLIQUE_MIX_DIGEST = 48
+ST_CLIQUE_UNCLE_HASH = 49
+ST_CLIQUE_DIFFICULTY = 50
+ST_CLIQUE_INVALID_TIMESTAMP = 51
+ST_CLIQUE_UNAUTHORIZED = 52
+ST_CLIQUE_VOTING_CHAIN = 53
 
 # a short text per per-item status: the reference's error string where it has one (include/gsv.h names
 # the sources)
@@ -100,6 +113,19 @@ STATUS_STRINGS = {
     ST_BITSET_UNREFERENCED_DATA: "extra bytes on input",
     ST_BITSET_EXCEEDED_TARGET: "target data size exceeded",
     ST_BITSET_ZERO_CONTENT: "zero byte in input content",
+    ST_CLIQUE_CHECKPOINT_BENEFICIARY: "beneficiary in checkpoint block non-zero",
+    ST_CLIQUE_INVALID_VOTE: "vote nonce not 0x00..0 or 0xff..f",
+    ST_CLIQUE_CHECKPOINT_VOTE: "vote nonce in checkpoint block non-zero",
+    ST_CLIQUE_MISSING_VANITY: "extra-data 32 byte vanity prefix missing",
+    ST_CLIQUE_MISSING_SIGNATURE: "extra-data 65 byte suffix signature missing",
+    ST_CLIQUE_EXTRA_SIGNERS: "non-checkpoint block contains extra signer list",
+    ST_CLIQUE_CHECKPOINT_SIGNERS: "invalid signer list on checkpoint block",
+    ST_CLIQUE_MIX_DIGEST: "non-zero mix digest",
+    ST_CLIQUE_UNCLE_HASH: "non empty uncle hash",
+    ST_CLIQUE_DIFFICULTY: "invalid difficulty",
+    ST_CLIQUE_INVALID_TIMESTAMP: "invalid timestamp",
+    ST_CLIQUE_UNAUTHORIZED: "unauthorized",
+    ST_CLIQUE_VOTING_CHAIN: "invalid voting chain",
 }
 
 SIGNER_EIP155 = 0
@@ -155,6 +181,8 @@ K_BLOOMBITS_BLOCKS = 37
 K_BLOOM_FILTER = 38
 K_RIDGE = 39  # GSV_K_RIDGE: gsv_ctx_kernel_time takes every id below it
 
+CLIQUE_RECORD_BYTES = 128  # the record of one header gsv_clique_fold reads (include/gsv.h "clique")
+
 ETHASH_MAX_CACHES = 3  # GSV_ETHASH_MAX_CACHES: epoch caches a context keeps for the ethash host forms
 ETHASH_MAX_DATASETS = 2  # GSV_ETHASH_MAX_DATASETS: epoch datasets a context keeps for the full and seal forms
 
@@ -197,6 +225,11 @@ class ChainConfigStruct(ctypes.Structure):
                 ("has_homestead", ctypes.c_uint8), ("has_dao_fork", ctypes.c_uint8), ("has_eip150", ctypes.c_uint8),
                 ("has_byzantium", ctypes.c_uint8), ("dao_fork_support", ctypes.c_uint8),
                 ("reserved", ctypes.c_uint8 * 3), ("eip150_hash", ctypes.c_uint8 * 32)]
+
+
+class CliqueConfigStruct(ctypes.Structure):
+    """gsv_clique_config (include/gsv.h): params.CliqueConfig"""
+    _fields_ = [("period", ctypes.c_uint64), ("epoch", ctypes.c_uint64)]
 
 
 # (name, restype, argtypes) for every symbol declared in include/gsv.h
@@ -302,6 +335,19 @@ SIGNATURES = [
     ("gsv_block_header_rules_dev", ctypes.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _u64, _vp, _vp, _vp, _vp, _vp, _vp,
                                                   _vp, _vp, _vp, _vp, _vp]),
     ("gsv_block_header_merge_dev", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    ("gsv_clique_snapshot_new", _vp, [_vp, _sz, _u64, _vp]),
+    ("gsv_clique_snapshot_from_genesis", _vp, [_vp, _sz, ctypes.POINTER(ctypes.c_int)]),
+    ("gsv_clique_snapshot_copy", _vp, [_vp]),
+    ("gsv_clique_snapshot_free", None, [_vp]),
+    ("gsv_clique_snapshot_number", _u64, [_vp]),
+    ("gsv_clique_snapshot_hash", ctypes.c_int, [_vp, _vp]),
+    ("gsv_clique_snapshot_signers", _sz, [_vp, _vp, _sz]),
+    ("gsv_clique_snapshot_recents", _sz, [_vp, _vp, _vp, _sz]),
+    ("gsv_clique_snapshot_votes", _sz, [_vp, _vp, _vp, _vp, _vp, _sz]),
+    ("gsv_clique_snapshot_tally", _sz, [_vp, _vp, _vp, _vp, _sz]),
+    ("gsv_clique_snapshot_inturn", ctypes.c_int, [_vp, _u64, _vp]),
+    ("gsv_clique_calc_difficulty", ctypes.c_int, [_vp, _vp]),
+    ("gsv_clique_fold", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, ctypes.POINTER(_sz)]),
     ("gsv_bloom9_batch", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp]),
     ("gsv_bloom9_batch_dev", ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
     ("gsv_receipts_work_bytes", _sz, [_sz, _u64]),

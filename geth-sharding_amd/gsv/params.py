@@ -2,6 +2,7 @@
 
     ChainConfig                      params/config.go:103-124 (the fields the ethash header rules read)
     MainnetChainConfig .. TestChainConfig    params/config.go:33-94
+    CliqueConfig                     params/config.go:134-138
     DAOForkBlockExtra, DAOForkExtraRange     params/dao.go:28, :32
     the protocol constants           params/protocol_params.go
 
@@ -22,10 +23,25 @@ DAOForkBlockExtra = bytes.fromhex("64616f2d686172642d666f726b")  # "dao-hard-for
 DAOForkExtraRange = 10
 
 
+class CliqueConfig:
+    """params.CliqueConfig: Period, the seconds between blocks to enforce; Epoch, the epoch length to reset votes and
+    checkpoint (0: the engine's default of 30000, clique.go:216-218)"""
+
+    def __init__(self, Period=0, Epoch=0):
+        self.Period, self.Epoch = int(Period), int(Epoch)
+        if not (0 <= self.Period < 1 << 64 and 0 <= self.Epoch < 1 << 64):
+            raise ValueError("params: Period and Epoch are uint64")
+
+    def as_struct(self) -> "_lib.CliqueConfigStruct":
+        """gsv_clique_config (include/gsv.h), as given: the engine defaults the epoch"""
+        return _lib.CliqueConfigStruct(self.Period, self.Epoch)
+
+
 class ChainConfig:
     def __init__(self, ChainId=None, HomesteadBlock=None, DAOForkBlock=None, DAOForkSupport=False, EIP150Block=None,
                  EIP150Hash=bytes(32), EIP155Block=None, EIP158Block=None, ByzantiumBlock=None,
-                 ConstantinopleBlock=None):
+                 ConstantinopleBlock=None, Clique=None):
+        self.Clique = Clique
         self.ChainId = ChainId
         self.HomesteadBlock = HomesteadBlock
         self.DAOForkBlock = DAOForkBlock
@@ -81,14 +97,19 @@ TestnetChainConfig = ChainConfig(
 RinkebyChainConfig = ChainConfig(
     ChainId=4, HomesteadBlock=1, DAOForkBlock=None, DAOForkSupport=True, EIP150Block=2,
     EIP150Hash=bytes.fromhex("9b095b36c15eaf13044373aef8ee0bd3a382a5abb92e402afa44b8249c3a90e9"), EIP155Block=3,
-    EIP158Block=3, ByzantiumBlock=1035301)
+    EIP158Block=3, ByzantiumBlock=1035301, Clique=CliqueConfig(Period=15, Epoch=30000))
 
 AllEthashProtocolChanges = ChainConfig(ChainId=1337, HomesteadBlock=0, DAOForkBlock=None, DAOForkSupport=False,
                                        EIP150Block=0, EIP155Block=0, EIP158Block=0, ByzantiumBlock=0)
 
+AllCliqueProtocolChanges = ChainConfig(ChainId=1337, HomesteadBlock=0, DAOForkBlock=None, DAOForkSupport=False,
+                                       EIP150Block=0, EIP155Block=0, EIP158Block=0, ByzantiumBlock=0,
+                                       Clique=CliqueConfig(Period=0, Epoch=30000))
+
 TestChainConfig = ChainConfig(ChainId=1, HomesteadBlock=0, DAOForkBlock=None, DAOForkSupport=False, EIP150Block=0,
                               EIP155Block=0, EIP158Block=0, ByzantiumBlock=0)
 
-__all__ = ["ChainConfig", "MainnetChainConfig", "TestnetChainConfig", "RinkebyChainConfig", "AllEthashProtocolChanges",
-           "TestChainConfig", "DAOForkBlockExtra", "DAOForkExtraRange", "MaximumExtraDataSize", "GasLimitBoundDivisor",
+__all__ = ["ChainConfig", "CliqueConfig", "MainnetChainConfig", "TestnetChainConfig", "RinkebyChainConfig",
+           "AllEthashProtocolChanges", "AllCliqueProtocolChanges", "TestChainConfig", "DAOForkBlockExtra",
+           "DAOForkExtraRange", "MaximumExtraDataSize", "GasLimitBoundDivisor",
            "MinGasLimit", "DifficultyBoundDivisor", "MinimumDifficulty", "DurationLimit"]

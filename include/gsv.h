@@ -82,6 +82,9 @@
  *   gsv_bloombits_match_batch  <- bloombits.NewMatcher and what a Matcher session computes
  *                                 (core/bloombits/matcher.go:92-131, :182-211, :337-366)
  *   gsv_bloom_filter_batch     <- bloomFilter (eth/filters/filter.go:278-305) after filters.New's flattening (:62-93)
+ *   gsv_clique_fold            <- the snapshot half of Clique.VerifyHeaders on the host: verifyCascadingFields'
+ *                                 checkpoint compare, verifySeal and Snapshot.apply over records of recovered signers
+ *                                 (consensus/clique/clique.go:351-367, :478-502, consensus/clique/snapshot.go:175-285)
  *
  * Conventions
  *   - Return value: GSV_SUCCESS (0) or a negative GSV_E_* API/HIP error. A bad ITEM never fails
@@ -174,6 +177,20 @@ extern "C" {
 #define GSV_ST_BITSET_UNREFERENCED_DATA 38 /* errUnreferencedData  "extra bytes on input"        :28 */
 #define GSV_ST_BITSET_EXCEEDED_TARGET 39   /* errExceededTarget    "target data size exceeded"   :32 */
 #define GSV_ST_BITSET_ZERO_CONTENT 40      /* errZeroContent       "zero byte in input content"  :36 */
+/* clique (gsv_clique_fold and the records it reads), in the order verifyHeader tests them: consensus/clique/clique.go */
+#define GSV_ST_CLIQUE_CHECKPOINT_BENEFICIARY 41 /* errInvalidCheckpointBeneficiary  :81, :280-282 */
+#define GSV_ST_CLIQUE_INVALID_VOTE 42           /* errInvalidVote                   :85, :284-286, snapshot.go:236-238 */
+#define GSV_ST_CLIQUE_CHECKPOINT_VOTE 43        /* errInvalidCheckpointVote         :89, :287-289 */
+#define GSV_ST_CLIQUE_MISSING_VANITY 44         /* errMissingVanity                 :93, :291-293 */
+#define GSV_ST_CLIQUE_MISSING_SIGNATURE 45      /* errMissingSignature              :97, :294-296, :178-180 */
+#define GSV_ST_CLIQUE_EXTRA_SIGNERS 46          /* errExtraSigners                  :101, :299-301 */
+#define GSV_ST_CLIQUE_CHECKPOINT_SIGNERS 47     /* errInvalidCheckpointSigners      :106, :302-304, :356-365 */
+#define GSV_ST_CLIQUE_MIX_DIGEST 48             /* errInvalidMixDigest              :109, :306-308 */
+#define GSV_ST_CLIQUE_UNCLE_HASH 49             /* errInvalidUncleHash              :112, :310-312 */
+#define GSV_ST_CLIQUE_DIFFICULTY 50             /* errInvalidDifficulty             :116, :314-318, :494-501 */
+#define GSV_ST_CLIQUE_INVALID_TIMESTAMP 51      /* ErrInvalidTimestamp              :120, :347-349 */
+#define GSV_ST_CLIQUE_UNAUTHORIZED 52           /* errUnauthorized                  :127, :483-493, snapshot.go:208-215 */
+#define GSV_ST_CLIQUE_VOTING_CHAIN 53           /* errInvalidVotingChain            :124, snapshot.go:181-188 */
 
 /* signer kinds for gsv_tx_sender_batch and gsv_tx_sign_batch (core/types/transaction_signing.go) */
 #define GSV_SIGNER_EIP155 0
@@ -923,6 +940,95 @@ int gsv_block_header_merge_dev(gsv_ctx *ctx, const uint8_t *d_pre_status, const 
                                const uint8_t *d_seals, const uint8_t *d_post_status, size_t n, uint8_t *d_status,
                                void *stream);
 
+/* ---- clique: the voting snapshot and the fold of Clique.VerifyHeaders (consensus/clique), host only ----
+ * The part of Clique.VerifyHeaders that is serial by nature runs here, on the host, over one RECORD per header that
+ * the caller packs from what is computed per header in parallel: Hash(), the signer (gsv_ecrecover_batch over sigHash,
+ * clique.go:146-168, and Extra[len - 65 :], :171-193) and the STATIC status, the checks of verifyHeader and
+ * verifyCascadingFields that need no snapshot, in the reference's order, first failure wins:
+ *    0. decode                                                             GSV_ST_BAD_RLP / GSV_ST_HEADER_TOO_WIDE
+ *    1. Time > now (full width; :275; no + 15 here)                        GSV_ST_FUTURE_BLOCK
+ *    2. checkpoint (Number % Epoch == 0) and Coinbase != 0 (:280)          GSV_ST_CLIQUE_CHECKPOINT_BENEFICIARY
+ *    3. Nonce neither ff..ff nor 00..00 (:284)                             GSV_ST_CLIQUE_INVALID_VOTE
+ *    4. checkpoint and Nonce != 0 (:287)                                   GSV_ST_CLIQUE_CHECKPOINT_VOTE
+ *    5. len(Extra) < 32 (:291)                                             GSV_ST_CLIQUE_MISSING_VANITY
+ *    6. len(Extra) < 97 (:294)                                             GSV_ST_CLIQUE_MISSING_SIGNATURE
+ *    7. not checkpoint and len(Extra) != 97 (:299)                         GSV_ST_CLIQUE_EXTRA_SIGNERS
+ *    8. checkpoint and (len(Extra) - 97) % 20 != 0 (:302)                  GSV_ST_CLIQUE_CHECKPOINT_SIGNERS
+ *    9. MixDigest != 0 (:306)                                              GSV_ST_CLIQUE_MIX_DIGEST
+ *   10. UncleHash != EmptyUncleHash (:310)                                 GSV_ST_CLIQUE_UNCLE_HASH
+ *   11. Number > 0 and Difficulty not 1 or 2 (:314)                        GSV_ST_CLIQUE_DIFFICULTY
+ *   12. misc.VerifyForkHashes (:320; clique has no DAO extra-data check)   GSV_ST_FORK_HASH
+ *   13. Number > 0: the parent in front decoded, its Number is Number - 1 (uint64) and its Hash() is ParentHash
+ *       (:344); else                                                       GSV_ST_UNKNOWN_ANCESTOR
+ *   14. Number > 0: parent.Time.Uint64() + Period > Time.Uint64(), in wrapping uint64 arithmetic on the low 64
+ *       bits as Go's (:347)                                                GSV_ST_CLIQUE_INVALID_TIMESTAMP
+ * The library has no device form of these per-header steps yet: the record is the contract such a form is to meet.
+ * A record is 128 bytes (csrc/clique_host.h):
+ *   hash 32 | parent_hash 32 | signer 20 | coinbase 20 | number 8 (little-endian) | extra_off 4 | extra_len 4 |
+ *   static status 1 | signer status 1 | vote 1 | difficulty 1 | zero 4
+ * extra_off is the offset of Extra's first byte from the header's first byte and extra_len its FULL length; the
+ * signer status is GSV_ST_OK, GSV_ST_INVALID_RECID, GSV_ST_RECOVER_FAILED, or GSV_ST_CLIQUE_MISSING_SIGNATURE when
+ * len(Extra) < 65; vote is 0 (Nonce 00..00, drop), 1 (ff..ff, authorize) or 2 (neither); difficulty is 1, 2, or 0
+ * for anything else; number is 0 for a header that did not decode or whose Number is wider than 8 bytes.
+ *
+ * The snapshot (snapshot.go:46-57) is an opaque gsv_clique_snapshot on the host: Number, Hash, Signers, Recents,
+ * Votes in order, Tally.  These calls need no device and no context.
+ *   new:          the snapshot at block `number` with hash `hash32` over n signers (newSnapshot, :62-76); NULL on a
+ *                 NULL hash or signer array
+ *   from_genesis: the snapshot at block 0 from an RLP-encoded genesis header: the signer list is Extra[32 : len - 65],
+ *                 (len - 97) / 20 addresses (clique.go:397-401), the hash the header's.  NULL and *status (NULL ok) =
+ *                 GSV_ST_BAD_RLP, GSV_ST_CLIQUE_MISSING_VANITY or GSV_ST_CLIQUE_MISSING_SIGNATURE otherwise
+ *   copy, free:   a deep copy (:104-127); free(NULL) is fine
+ *   number, hash: the block the snapshot stands at
+ *   signers:      ascending (snapshot.go:288-301); recents: by ascending block; votes: chronological; tally: by
+ *                 ascending address.  Each returns the count and fills at most `cap` entries of the arrays that are
+ *                 not NULL (signer20 / address20 rows of 20 bytes, block uint64, authorize uint8, votes int32)
+ *   inturn:       Snapshot.inturn (:304-310), 0 for an empty signer set (the reference divides by zero)
+ *   gsv_clique_calc_difficulty: CalcDifficulty(snap, signer) (clique.go:669-676): 2 in turn at snap.Number + 1, else 1
+ *
+ * gsv_clique_fold(snap, config, records, n, rlp, off, status, applied): verifyCascadingFields' snapshot half, verifySeal
+ * and Snapshot.apply over the records of n consecutive headers.  snap is at the parent of header 0 and is moved to
+ * the last header applied.  rlp / off are the caller's headers on the HOST (read only for a checkpoint's signer list,
+ * at the record's offsets).  With a sticky error err = GSV_ST_OK, status[i] is
+ *   1. the static status if it is not GSV_ST_OK;
+ *   2. else GSV_ST_OK if Number == 0 (verifyCascadingFields returns nil, clique.go:334), and nothing is applied;
+ *   3. else err if it is not GSV_ST_OK (snapshot() failed on an earlier header, :351-354);
+ *   4. else for a checkpoint: GSV_ST_CLIQUE_CHECKPOINT_SIGNERS if Extra[32 : len - 65] is not the snapshot's sorted
+ *      signers (:356-365);
+ *   5. else verifySeal (:478-502): the signer status; the signer not in Signers: GSV_ST_CLIQUE_UNAUTHORIZED; a recent
+ *      signer with seen > number - limit (limit = len(Signers) / 2 + 1, uint64): GSV_ST_CLIQUE_UNAUTHORIZED; the turn
+ *      rule against Difficulty (in turn 2, else 1): GSV_ST_CLIQUE_DIFFICULTY.
+ * Then header i is applied exactly as Snapshot.apply does (snapshot.go:192-280), WHATEVER status[i] was (the reference
+ * applies a parent that failed verifyHeader, too): the epoch reset, the oldest recent dropped, the signer status,
+ * unauthorized, recent, the previous vote uncast, the nonce read as a vote (GSV_ST_CLIQUE_INVALID_VOTE), cast,
+ * majority, the signer added or dropped with the second recents delete, votes by and about the account discarded.
+ * GSV_ST_CLIQUE_VOTING_CHAIN when Number != snap.Number + 1 (:181-188).  A failing apply sets err, leaves the snapshot
+ * at the last header applied and stops the count in *applied (NULL ok).
+ * OURS, not the reference's: a header that did not decode, or whose ParentHash is not the snapshot's Hash (for header
+ * 0: the caller's snapshot is not at its parent), sets err = GSV_ST_UNKNOWN_ANCESTOR.  The reference would walk to its
+ * database for the missing ancestors (clique.go:408-425), which the call does not have.
+ * GSV_E_INVALID_ARG: a NULL snapshot, configuration, record or status array, rlp or off NULL with n > 0, epoch == 0. */
+typedef struct gsv_clique_config {
+    uint64_t period; /* params.CliqueConfig.Period */
+    uint64_t epoch;  /* params.CliqueConfig.Epoch; 0 is GSV_E_INVALID_ARG (clique.New defaults it to 30000: the caller's) */
+} gsv_clique_config;
+typedef struct gsv_clique_snapshot gsv_clique_snapshot;
+gsv_clique_snapshot *gsv_clique_snapshot_new(const uint8_t *signers20, size_t n, uint64_t number, const uint8_t *hash32);
+gsv_clique_snapshot *gsv_clique_snapshot_from_genesis(const uint8_t *header_rlp, size_t len, int *status);
+gsv_clique_snapshot *gsv_clique_snapshot_copy(const gsv_clique_snapshot *snap);
+void gsv_clique_snapshot_free(gsv_clique_snapshot *snap);
+uint64_t gsv_clique_snapshot_number(const gsv_clique_snapshot *snap);
+int gsv_clique_snapshot_hash(const gsv_clique_snapshot *snap, uint8_t *hash32);
+size_t gsv_clique_snapshot_signers(const gsv_clique_snapshot *snap, uint8_t *signer20, size_t cap);
+size_t gsv_clique_snapshot_recents(const gsv_clique_snapshot *snap, uint64_t *block, uint8_t *signer20, size_t cap);
+size_t gsv_clique_snapshot_votes(const gsv_clique_snapshot *snap, uint8_t *signer20, uint64_t *block,
+                                 uint8_t *address20, uint8_t *authorize, size_t cap);
+size_t gsv_clique_snapshot_tally(const gsv_clique_snapshot *snap, uint8_t *address20, uint8_t *authorize,
+                                 int32_t *votes, size_t cap);
+int gsv_clique_snapshot_inturn(const gsv_clique_snapshot *snap, uint64_t number, const uint8_t *signer20);
+int gsv_clique_calc_difficulty(const gsv_clique_snapshot *snap, const uint8_t *signer20);
+int gsv_clique_fold(gsv_clique_snapshot *snap, const gsv_clique_config *config, const uint8_t *records, size_t n,
+                    const uint8_t *rlp, const uint64_t *off, uint8_t *status, size_t *applied);
 /* ---- synthetic signed workload (bench / test data generator; signing is not on the path) ----
  * key_i, msg_i, nonce_i = Keccak256(le64(seed) || le64(i) || "key"/"msg"/"nce"), key and nonce
  * reduced mod n (0 -> 1); sig_i = ECDSA(key_i, msg_i, nonce_i), low-s normalised, recid in sig[64].
