@@ -1,7 +1,10 @@
 """The seeded corpus of modexp precompile inputs shared by tests/test_modexp_cpu.py and
 tests/test_gpu_modexp.py: both sides of every width-class edge and limb edge of the modulus, bases shorter,
 equal and longer than it, odd / even / power-of-two / degenerate moduli, and the encodings getData pads or
-cuts.  Expectations are never stored here: they come from tests/modexp_model.py."""
+cuts; and the shapes of the device form (dev_shapes, rows, two_trip_rows), which tests/test_gpu_modexp_shapes.py
+launches and tests/test_modexp_cpu.py feeds to the host build of the arithmetic: modulus lengths at every
+residue mod 4 on both sides of every class, bases with a partial top piece, and a launch whose first waves
+come round a second time.  Expectations are never stored here: they come from tests/modexp_model.py."""
 import random
 
 MOD_LENS = (1, 3, 4, 5, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 1023, 1024)
@@ -137,6 +140,154 @@ def items(seed=198):
                              rng.choice(BASE_KINDS), ek))
     out += encodings(rng)
     return out
+
+
+# ---------------------------------------------------------------- shapes of the device form
+# A launch of the device form has one (bl, el, ml) for all its rows, so these lengths reach the kernel as they
+# are: nothing pads them to a class width as the host form's grouping does.
+NCLASS = 6
+WIDE_EXP_FIELD = 1024  # an exponent field this wide holds a value of at most 16 bits behind its zero bytes
+# Classes whose modulus lengths are thinned to one length = 1 (mod 4) just above the class's lower edge and
+# one = 3 (mod 4) just below its upper edge.  Empty: every class runs its eight lengths (the durations are in
+# the commit that added tests/test_gpu_modexp_shapes.py).
+THIN_CLASSES = ()
+BASE_LEN_KINDS = ("0", "1", "ml-1", "ml+1", "4L+1", "8L-1", "1024")
+
+
+def class_limbs(c):
+    return 8 << c
+
+
+def class_edges(c):
+    """(lo, hi): the shortest and the longest modulus of class c, in bytes"""
+    return (2 * class_limbs(c) + 1 if c else 1), 4 * class_limbs(c)
+
+
+def width_class(ml):
+    return next(c for c in range(NCLASS) if ml <= class_edges(c)[1])
+
+
+def class_mod_lens(c):
+    """every residue mod 4 at both edges of the class"""
+    lo, hi = class_edges(c)
+    if c in THIN_CLASSES:
+        return [lo, hi - 1]
+    return [lo, lo + 1, lo + 2, lo + 3, hi - 3, hi - 2, hi - 1, hi]
+
+
+def base_len(kind, ml):
+    L = class_limbs(width_class(ml))
+    v = {"0": 0, "1": 1, "ml-1": ml - 1, "ml+1": ml + 1, "4L+1": 4 * L + 1, "8L-1": 8 * L - 1, "1024": 1024}[kind]
+    return min(v, 1024)
+
+
+def class_exp_lens(c):
+    return (0, 1, 2) if class_edges(c)[0] >= SMALL_EXP_FROM else (0, 1, 3, 33)
+
+
+def dev_shapes(c=None):
+    """(bl, el, ml) of the launches of class c (of every class in turn for None), without repeats.  Every
+    kind of base length meets a non-zero exponent at a modulus length that is no multiple of 4, in turn over
+    those lengths; the lengths that are a multiple of 4 get a base one byte longer and one byte shorter;
+    el = 0 comes with bl = 0 at the shortest modulus and with a longer base; the 1024-byte exponent field
+    comes once, at the length = 3 (mod 4) below the upper edge."""
+    if c is None:
+        return [s for k in range(NCLASS) for s in dev_shapes(k)]
+    mls = class_mod_lens(c)
+    ragged = [m for m in mls if m % 4]
+    els = [e for e in class_exp_lens(c) if e]
+    out = []
+    for i, kind in enumerate(BASE_LEN_KINDS):
+        ml = ragged[i % len(ragged)]
+        out.append((base_len(kind, ml), els[i % len(els)], ml))
+    for i, ml in enumerate(m for m in mls if m % 4 == 0):
+        out.append((base_len(("ml+1", "ml-1")[i % 2], ml), els[(i + 1) % len(els)], ml))
+    out.append((0, 0, ragged[0]))
+    out.append((base_len("ml+1", ragged[-2]), 0, ragged[-2]))
+    out.append((base_len("ml+1", ragged[-1]), WIDE_EXP_FIELD, ragged[-1]))
+    return list(dict.fromkeys(out))
+
+
+def row_kinds(i):
+    """(modulus kind, base kind, exponent kind) of row i of rows(): the modulus kinds turn by lane, so that
+    neighbouring lanes of a wave take different paths; the exponent kinds turn by row, one step further every
+    seven rows, so that they meet every base kind"""
+    return MOD_KINDS[i % len(MOD_KINDS)], BASE_KINDS[i % len(BASE_KINDS)], EXP_KINDS[(i + i // 7) % len(EXP_KINDS)]
+
+
+def _row(rng, bl, el, ml, mk, bk, ek):
+    m = modulus(rng, mk, ml)
+    b = base(rng, bk, bl, int.from_bytes(m, "big"))
+    if el >= WIDE_EXP_FIELD:
+        e = exponent(rng, ek, 2, True).rjust(el, b"\0")
+    else:
+        e = exponent(rng, ek, el, ml >= SMALL_EXP_FROM)
+    return b + e + m
+
+
+def rows(rng, n, bl, el, ml, start=0):
+    """n rows base || exp || mod of one shape, of the kinds row_kinds(start), row_kinds(start + 1), ..."""
+    return [_row(rng, bl, el, ml, *row_kinds(start + i)) for i in range(n)]
+
+
+def model_rows(M, rws, bl, el, ml):
+    """the model's outputs of rows of one shape, joined (M is tests/modexp_model.py)"""
+    hdr = word(bl) + word(el) + word(ml)
+    return b"".join(M.run(hdr + r) for r in rws)
+
+
+# ---------------------------------------------------------------- the second trip of the grid-stride loop
+MAX_WAVES = 2048                  # csrc/modexp_plan.h: a launch of a wide class has at most this many waves
+TWO_TRIP_LANES = MAX_WAVES * 64   # the stride of such a launch
+TWO_TRIP_FIRST = 128              # rows 0 .. 127: the first items of the lanes of waves 0 and 1
+TWO_TRIP_SECOND = 70              # rows TWO_TRIP_LANES .. + 69: the second items of wave 0 and of six lanes of wave 1
+TWO_TRIP_N = TWO_TRIP_LANES + TWO_TRIP_SECOND
+# the modulus kind of a lane's second item, by the kind of its first (in the order of MOD_KINDS): every pair
+# differs in path, an even modulus with k >= 32 meets an odd one or a power of two and the reverse, and the
+# zero modulus (which leaves the item before anything is written) comes both before and after an odd one
+SECOND_MOD_KINDS = ("zero", "k33", "k32", "2q", "odd", "pow2", "ff", "odd", "pow2", "top0", "k33", "one")
+_NONZERO_EXP_KINDS = tuple(k for k in EXP_KINDS if k != "zero")
+
+
+def two_trip_real():
+    """indices of the rows of two_trip_rows() that do work"""
+    return list(range(TWO_TRIP_FIRST)) + list(range(TWO_TRIP_LANES, TWO_TRIP_N))
+
+
+def two_trip_rows(rng, ml, bl, el):
+    """(TWO_TRIP_N, bl + el + ml) uint8: the rows of one launch whose waves 0 and 1 come round a second time.
+    The rows of two_trip_real() are of the kinds of rows() with non-zero exponents, the second item of a lane
+    of the kind SECOND_MOD_KINDS gives; every other row is row TWO_TRIP_FIRST, an odd modulus under an
+    all-zero exponent, which the kernel answers with 1 once it has loaded the modulus."""
+    import numpy as np
+    assert el > 0 and ml > 1
+
+    def real(i, mk):
+        _, bk, _ = row_kinds(i)
+        ek = _NONZERO_EXP_KINDS[i % len(_NONZERO_EXP_KINDS)]
+        r = bytearray(_row(rng, bl, el, ml, mk, bk, ek))
+        if not any(r[bl:bl + el]):
+            r[bl + el - 1] = 1
+        return bytes(r)
+
+    idle = base(rng, "longer", bl, 0) + bytes(el) + modulus(rng, "odd", ml)
+    out = np.tile(np.frombuffer(idle, np.uint8), (TWO_TRIP_N, 1))
+    for i in range(TWO_TRIP_FIRST):
+        out[i] = np.frombuffer(real(i, MOD_KINDS[i % len(MOD_KINDS)]), np.uint8)
+    for j in range(TWO_TRIP_SECOND):
+        out[TWO_TRIP_LANES + j] = np.frombuffer(real(j + 3, SECOND_MOD_KINDS[j % len(MOD_KINDS)]), np.uint8)
+    return out
+
+
+def two_trip_want(M, arr, bl, el, ml):
+    """the model's (TWO_TRIP_N, ml) outputs of two_trip_rows(): the real rows one by one, the idle row once"""
+    import numpy as np
+    hdr = word(bl) + word(el) + word(ml)
+    idle = np.frombuffer(M.run(hdr + arr[TWO_TRIP_FIRST].tobytes()), np.uint8)
+    want = np.tile(idle, (TWO_TRIP_N, 1))
+    for i in two_trip_real():
+        want[i] = np.frombuffer(M.run(hdr + arr[i].tobytes()), np.uint8)
+    return want
 
 
 def mixed_wave(seed=5, n=193, ml=32):

@@ -82,19 +82,11 @@ def test_mixed_waves_of_one_class(ctx):
 
 
 # ---------------------------------------------------------------- (d) the device-resident form
-def _rows(rng, n, bl, el, ml):
-    """n rows base || exp || mod of one shape, moduli odd, even, a power of two and zero in turn"""
-    kinds = ("odd", "2q", "odd", "k33", "pow2", "zero", "odd", "top0")
-    rows = []
-    for i in range(n):
-        m = C.modulus(rng, kinds[i % len(kinds)], ml)
-        rows.append(bytes(rng.getrandbits(8) for _ in range(bl)) + bytes(rng.getrandbits(8) for _ in range(el)) + m)
-    return rows
+_rows = C.rows  # n rows base || exp || mod of one shape, the kinds of modulus, base and exponent in turn
 
 
 def _model_rows(rows, bl, el, ml):
-    hdr = C.word(bl) + C.word(el) + C.word(ml)
-    return b"".join(M.run(hdr + r) for r in rows)
+    return C.model_rows(M, rows, bl, el, ml)
 
 
 @pytest.mark.parametrize("shape", [(32, 32, 32), (256, 3, 256), (1, 0, 1), (5, 2, 3), (33, 1, 32), (1024, 2, 1024)])

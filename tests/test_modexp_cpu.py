@@ -201,8 +201,121 @@ def test_python_mirror_checks_before_any_call():
         c.modexp_batch_dev(T(2, 32 + 32 + 64), 32, 32, 64, T(2, 64), work_t=None)
 
 
+# ---------------------------------------------------------------- the shapes of the device form
+def test_dev_shapes_cover_every_class():
+    shapes = C.dev_shapes()
+    assert len(shapes) == len(set(shapes)) and shapes == [s for c in range(C.NCLASS) for s in C.dev_shapes(c)]
+    for c in range(C.NCLASS):
+        L = C.class_limbs(c)
+        lo, hi = C.class_edges(c)
+        assert (lo, hi) == ((1 if c == 0 else 2 * L + 1), 4 * L)
+        own = C.dev_shapes(c)
+        assert all(lo <= ml <= hi and C.width_class(ml) == c and bl <= 1024 and el <= 1024 for bl, el, ml in own)
+        mls = {ml for _, _, ml in own}
+        full = {lo, lo + 1, lo + 2, lo + 3, hi - 3, hi - 2, hi - 1, hi}
+        assert mls == (full if c not in C.THIN_CLASSES else {lo, hi - 1})
+        assert lo % 4 == 1 and (hi - 1) % 4 == 3 and {lo, hi - 1} <= mls  # the floor of any thinning
+        assert set(C.THIN_CLASSES) <= {4, 5}
+        # every kind of base length at a modulus that is no multiple of 4, under an exponent that does work
+        ragged = {(bl, ml) for bl, el, ml in own if ml % 4 and 0 < el < C.WIDE_EXP_FIELD}
+        for kind in C.BASE_LEN_KINDS:
+            assert any(bl == C.base_len(kind, ml) for bl, ml in ragged), (c, kind)
+        if 8 * L - 1 <= 1024:
+            # a top piece of one byte, and one that is one byte short of full
+            assert any(bl == 4 * L + 1 for bl, _ in ragged) and any(bl == 8 * L - 1 for bl, _ in ragged)
+        assert any(0 < bl < ml for bl, ml in ragged) and any(bl == 0 for bl, _ in ragged)
+        want_el = {0, 1, 2} if c >= 4 else {0, 1, 3, 33}
+        assert {el for _, el, _ in own} == want_el | {1024}
+        assert sum(el == 1024 for _, el, _ in own) == 1 and (0, 0, lo) in own
+    # rows: every kind of modulus among 12 neighbouring lanes, every (modulus, base) and (base, exponent) pair
+    # in a launch of 130; a 1024-byte exponent field holds 16 bits at the most
+    kinds = [C.row_kinds(i) for i in range(130)]
+    assert {k[0] for k in kinds[:12]} == set(C.MOD_KINDS) == {k[0] for k in kinds[118:]}
+    assert {(k[0], k[1]) for k in kinds} == {(m, b) for m in C.MOD_KINDS for b in C.BASE_KINDS}
+    assert {(k[1], k[2]) for k in kinds} == {(b, e) for b in C.BASE_KINDS for e in C.EXP_KINDS}
+    rng = __import__("random").Random(3)
+    for bl, el, ml in ((40, 1024, 39), (5, 3, 3), (0, 0, 1), (1024, 2, 1021)):
+        rws = C.rows(rng, 130, bl, el, ml)
+        assert len(rws) == 130 and all(len(r) == bl + el + ml for r in rws)
+        exps = [int.from_bytes(r[bl:bl + el], "big") for r in rws]
+        if el == 1024:
+            assert max(exps) == 0xFFFF and min(exps) == 0
+        mods = [int.from_bytes(r[bl + el:], "big") for r in rws]
+        assert mods[4] == 0 and mods[3] == 1 and mods[0] % 2 == 1
+
+
+def _path(m):
+    """what an item's modulus makes the kernel do: "zero", or (k > 0, q == 1) for m = 2^k q"""
+    if m == 0:
+        return "zero"
+    k = (m & -m).bit_length() - 1
+    return (k > 0, m >> k == 1)
+
+
+@pytest.fixture(scope="module")
+def two_trips():
+    """[(L, bl, el, ml, rows, the model's outputs)] of tests/test_gpu_modexp_shapes.py test_second_trip"""
+    out = []
+    for L, ml in ((16, 37), (128, 259)):
+        bl, el = ml + 1, 2
+        arr = C.two_trip_rows(__import__("random").Random(L), ml, bl, el)
+        out.append((L, bl, el, ml, arr, C.two_trip_want(M, arr, bl, el, ml)))
+    return out
+
+
+def test_two_trip_rows(two_trips):
+    n, lanes = 2048 * 64 + 70, 2048 * 64
+    assert (C.TWO_TRIP_N, C.TWO_TRIP_LANES, C.MAX_WAVES) == (n, lanes, 2048)
+    txt = open(os.path.join(ROOT, "geth-sharding_amd", "csrc", "modexp_plan.h")).read()
+    assert int(re.search(r"MAX_WAVES = (\d+);", txt).group(1)) == C.MAX_WAVES
+    real = C.two_trip_real()
+    assert real == list(range(128)) + list(range(lanes, lanes + 70))
+    for L, bl, el, ml, arr, want in two_trips:
+        assert arr.shape == (n, bl + el + ml) and arr.dtype == np.uint8 and want.shape == (n, ml)
+        assert C.class_limbs(C.width_class(ml)) == L
+        exp = lambda i: int.from_bytes(arr[i, bl:bl + el].tobytes(), "big")
+        mod = lambda i: int.from_bytes(arr[i, bl + el:].tobytes(), "big")
+        assert all(exp(i) > 0 for i in real)
+        # every other row is the one idle row: an odd modulus under a zero exponent, answered with 1
+        idle = np.ones(n, bool)
+        idle[real] = False
+        assert (arr[idle] == arr[128]).all() and exp(128) == 0 and mod(128) % 2 == 1 and mod(128) > 1
+        assert (want[idle] == want[128]).all() and int.from_bytes(want[128].tobytes(), "big") == 1
+        for i in real:
+            assert want[i].tobytes() == M.run(C.word(bl) + C.word(el) + C.word(ml) + arr[i].tobytes())
+        # a lane's two items differ in path
+        pairs = [(_path(mod(j)), _path(mod(lanes + j))) for j in range(70)]
+        assert sum(a != b for a, b in pairs) >= 40
+        odd = (False, False)
+        assert ("zero", odd) in pairs and (odd, "zero") in pairs
+        wide = lambda i: mod(i) and (mod(i) & -mod(i)).bit_length() - 1 >= 32 and _path(mod(i)) == (True, False)
+        plain = lambda i: mod(i) and (mod(i) % 2 == 1 or _path(mod(i))[1])  # odd, or a power of two
+        assert any(wide(j) and plain(lanes + j) for j in range(70))
+        assert any(plain(j) and wide(lanes + j) for j in range(70))
+        assert {_path(mod(j)) for j in range(12)} == {"zero", (False, False), (False, True), (True, False), (True, True)}
+
+
 # ---------------------------------------------------------------- the arithmetic, as host code under sanitizers
-def test_device_arithmetic_as_host_code_under_sanitizers(tmp_path, corpus, vectors):
+@pytest.fixture(scope="module")
+def host_exe(tmp_path_factory):
+    """tests/native/modexp_host_main.cpp with ASan + UBSan (a plain build where the compiler links neither)"""
+    src = os.path.join(ROOT, "tests", "native", "modexp_host_main.cpp")
+    exe = tmp_path_factory.mktemp("modexp_host") / "modexp_host_main"
+    base = ["g++", "-O2", "-g", "-std=c++17", "-Wall", "-o", str(exe), src]
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
+    if subprocess.run(base + san, capture_output=True).returncode != 0:
+        subprocess.run(base, check=True)
+    return str(exe)
+
+
+def _write_items(path, pairs):
+    with open(path, "wb") as f:
+        f.write(struct.pack("<I", len(pairs)))
+        for inp, out in pairs:
+            f.write(struct.pack("<II", len(inp), len(out)) + inp + out)
+
+
+def test_device_arithmetic_as_host_code_under_sanitizers(tmp_path, host_exe, corpus, vectors):
     """csrc/modexp_dev.cuh and csrc/modexp_plan.h as a stand-alone program with ASan + UBSan (a plain build
     where the compiler links neither), run as a child process over the vectors, the corpus and the mixed wave of
     the GPU test, through every width class: tests/native/modexp_host_main.cpp"""
@@ -210,15 +323,31 @@ def test_device_arithmetic_as_host_code_under_sanitizers(tmp_path, corpus, vecto
     pairs = [(inp, e) for _, inp, e in vectors] + [(b, out) for (_, b), (_, out) in zip(items, exp)]
     pairs += [(b, M.run(b)) for b in C.mixed_wave()]
     data = tmp_path / "modexp_items.bin"
-    with open(data, "wb") as f:
-        f.write(struct.pack("<I", len(pairs)))
-        for inp, out in pairs:
-            f.write(struct.pack("<II", len(inp), len(out)) + inp + out)
-    src = os.path.join(ROOT, "tests", "native", "modexp_host_main.cpp")
-    exe = tmp_path / "modexp_host_main"
-    base = ["g++", "-O2", "-g", "-std=c++17", "-Wall", "-o", str(exe), src]
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
-    if subprocess.run(base + san, capture_output=True).returncode != 0:
-        subprocess.run(base, check=True)
-    r = subprocess.run([str(exe), str(data)], capture_output=True, text=True, timeout=300)
+    _write_items(data, pairs)
+    r = subprocess.run([host_exe, str(data)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
+
+
+def test_interleaved_region_and_dirty_slots_under_sanitizers(tmp_path, host_exe, two_trips):
+    """The instantiation the kernel runs, modexp_item<L, 64, false> on the columns of a wave's region of
+    exactly work_bytes, for every class: the rows of dev_shapes() (twelve rows a shape, five in the two widest
+    classes, the kinds moving on from shape to shape), then the twice-used lanes of two_trip_rows(), a lane's
+    first item and then its second.  The program runs the items of a class one after the other in one column
+    that is never cleared, and each of them again on slots of 0x00, of 0xFF and of a pattern."""
+    rng = __import__("random").Random(64)
+    pairs = []
+    for k, (bl, el, ml) in enumerate(C.dev_shapes()):
+        per = 5 if ml >= C.SMALL_EXP_FROM else 12
+        hdr = C.word(bl) + C.word(el) + C.word(ml)
+        pairs += [(hdr + r, M.run(hdr + r)) for r in C.rows(rng, per, bl, el, ml, start=k * per)]
+    for L, bl, el, ml, arr, want in two_trips:
+        hdr = C.word(bl) + C.word(el) + C.word(ml)
+        for j in range(C.TWO_TRIP_SECOND):
+            for i in (j, C.TWO_TRIP_LANES + j):
+                pairs.append((hdr + arr[i].tobytes(), want[i].tobytes()))
+    assert {C.width_class(M.lengths(inp)[2]) for inp, _ in pairs} == set(range(C.NCLASS))
+    data = tmp_path / "modexp_region.bin"
+    _write_items(data, pairs)
+    r = subprocess.run([host_exe, "--region", str(data)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
+    assert "%d runs" % (4 * len(pairs)) in r.stderr
